@@ -1,9 +1,16 @@
 """Benchmark: training-step edges/sec on batches of 2394-fiber x 128-class
-complete bipartite graphs (BASELINE.json metric), plus the HBM roofline of the
-dominant kernel and the CPU oracle timed on the host.
+complete bipartite graphs (BASELINE.json metric); with --full also the HBM
+roofline of the dominant kernel and the CPU oracle timed on the host.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--graphs G] [--blocks B]
-                    [--fibers NF] [--classes NC]
+                    [--fibers NF] [--classes NC] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes the last step's
+results if --dump-outputs is given, and prints the JSON line (``roofline`` and
+``cpu_baseline`` null).  --full adds every other measurement after the timed
+region: the per-kernel in-graph and eager durations and the roofline, the other
+edge paths (``alt_paths``), the CPU baseline, and at N > 1 the eager tail
+timings and the rank-consistency check.
 
 Default workload: BASELINE.json's metric config (16 graphs of 2394x128 per
 GPU, 8 blocks).  configs[2] of BASELINE.json (a batch of 256 synthetic
@@ -102,7 +109,35 @@ def parse():
     ap.add_argument("--alt-paths", default="mfma,bf16x3,mfma32",
                     help="other edge paths whose step rate is measured after the headline "
                          "one (N=1, graph replay; reported in alt_paths; '' for none)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the per-kernel durations and the "
+                         "roofline, the --alt-paths, the CPU baseline (--no-cpu-baseline, "
+                         "--cpu-seconds) and, at N > 1, the eager tail and the rank consistency; "
+                         "without it those options have no effect")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, gradients, parameters, "
+                         "BatchNorm buffers) to DIR/<name>.npy")
     return ap.parse_args()
+
+
+def dump_outputs(dirname, loss, gnn):
+    """What a caller of the timed step holds after its last call, as
+    DIR/<name>.npy: the loss the step returns (float32), the gradients its
+    backward left and the parameters its Adam update left (float32, each
+    flattened in named_parameters() order), and the BatchNorm buffers its
+    forward updated (float64: running statistics and batch counts, in
+    named_buffers() order).  A few hundred KB in all; reads only."""
+    os.makedirs(dirname, exist_ok=True)
+    params = list(gnn.parameters())
+    grads = [p.grad if p.grad is not None else torch.zeros_like(p) for p in params]
+    arrays = {
+        "loss": loss.detach().reshape(1).float(),
+        "gradients": torch.cat([g.detach().reshape(-1).float() for g in grads]),
+        "parameters": torch.cat([p.detach().reshape(-1).float() for p in params]),
+        "buffers": torch.cat([b.detach().reshape(-1).double() for b in gnn.buffers()]),
+    }
+    for name, t in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), t.cpu().numpy())
 
 
 def make_batch(G, rank, device):
@@ -435,6 +470,65 @@ def main():
     # no device-wide barrier of the fused class-side launches timed out
     sync_faults = native.sync_faults()
     assert sync_faults == 0, f"{sync_faults} device-wide barrier time-outs"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, gnn)
+
+    def report(roofline=None, cpu=None, tail=None, consistency=None, alt=None):
+        """Rank 0 prints the JSON line; the process group is torn down."""
+        if rank == 0:
+            value = world * E * args.steps / elapsed
+            if NC == 16 and G * world == 2048:
+                bcfg = (f"BASELINE configs[3]: 2048 synthetic {NF}x{NC} graphs sharded over "
+                        f"{world} GPU(s), {G} per GPU, RCCL gradient all-reduce")
+            elif NC == 16 and G == 256 and world == 1:
+                bcfg = f"BASELINE configs[2]: 256 synthetic {NF}x{NC} graphs on one GPU"
+            elif (NF, NC, B) == (2394, 128, 8):
+                bcfg = ("BASELINE metric / configs[4] shape (2394x128, 8 message-passing rounds)" +
+                        (f", weak-scaled over {world} GPUs (configs[3]'s data-parallel sharding)"
+                         if world > 1 else ""))
+            else:
+                bcfg = None
+            metric = "training-step edges/sec on 2394\u00d7128 bipartite batches; % HBM roofline"
+            if (NF, NC) != (2394, 128):
+                metric = (f"training-step edges/sec on {NF}\u00d7{NC} bipartite batches; "
+                          f"% HBM roofline")
+            line = {
+                "metric": metric,
+                "value": value, "unit": "edges/s", "n_gpus": world, "steps": args.steps,
+                "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
+                "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+                "dtype": DTYPE[args.edge_path],
+                "data": "synthetic",
+                "precision": PRECISION[args.edge_path],
+                "meets_fp32_tolerance": MEETS_FP32_TOL[args.edge_path],
+                "config": {"workload": f"{G} complete bipartite {NF}x{NC} graphs per GPU, {B} "
+                                       f"message-passing blocks, Fdim {FDIM}; full training step "
+                                       f"(GNN fwd + train.py loss + bwd + Adam)",
+                           "fibers": NF, "classes": NC, "graphs_per_gpu": G,
+                           "global_graphs": G * world, "blocks": B, "fdim": FDIM,
+                           "edges_per_gpu_step": E, "parallelism": f"dp{world}",
+                           "baseline_config": bcfg},
+                "full": args.full,
+                "roofline": roofline,
+                "cpu_baseline": cpu,
+            }
+            line["sync_faults"] = sync_faults
+            if consistency is not None:
+                line["rank_consistency"] = consistency
+            if tail is not None:
+                line["eager_tail"] = tail
+            if alt:
+                line["alt_paths"] = alt
+            print(json.dumps(line), flush=True)
+        if dist_path:
+            dist.destroy_process_group()
+
+    # a plain run ends here: everything below measures or checks something
+    # other than the headline figure, in runs of its own
+    if not args.full:
+        report()
+        return
+
     # ---- N > 1: the tail of a step -- the buffer broadcast before the
     # forward, the gradient all-reduce and Adam after the backward -- each run
     # eagerly and timed alone (synchronised) over a few extra steps
@@ -638,53 +732,10 @@ def main():
     if in_graph:
         roofline["in_graph"] = in_graph
 
-    if rank == 0:
-        cpu = None
-        if world == 1 and not args.no_cpu_baseline:
-            cpu = cpu_baseline(B, args.cpu_seconds)
-        value = world * E * args.steps / elapsed
-        if NC == 16 and G * world == 2048:
-            bcfg = (f"BASELINE configs[3]: 2048 synthetic {NF}x{NC} graphs sharded over "
-                    f"{world} GPU(s), {G} per GPU, RCCL gradient all-reduce")
-        elif NC == 16 and G == 256 and world == 1:
-            bcfg = f"BASELINE configs[2]: 256 synthetic {NF}x{NC} graphs on one GPU"
-        elif (NF, NC, B) == (2394, 128, 8):
-            bcfg = ("BASELINE metric / configs[4] shape (2394x128, 8 message-passing rounds)" +
-                    (f", weak-scaled over {world} GPUs (configs[3]'s data-parallel sharding)"
-                     if world > 1 else ""))
-        else:
-            bcfg = None
-        metric = "training-step edges/sec on 2394\u00d7128 bipartite batches; % HBM roofline"
-        if (NF, NC) != (2394, 128):
-            metric = f"training-step edges/sec on {NF}\u00d7{NC} bipartite batches; % HBM roofline"
-        line = {
-            "metric": metric,
-            "value": value, "unit": "edges/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": DTYPE[args.edge_path],
-            "data": "synthetic",
-            "precision": PRECISION[args.edge_path],
-            "meets_fp32_tolerance": MEETS_FP32_TOL[args.edge_path],
-            "config": {"workload": f"{G} complete bipartite {NF}x{NC} graphs per GPU, {B} "
-                                   f"message-passing blocks, Fdim {FDIM}; full training step "
-                                   f"(GNN fwd + train.py loss + bwd + Adam)",
-                       "fibers": NF, "classes": NC, "graphs_per_gpu": G, "global_graphs": G * world,
-                       "blocks": B, "fdim": FDIM, "edges_per_gpu_step": E,
-                       "parallelism": f"dp{world}", "baseline_config": bcfg},
-            "roofline": roofline,
-            "cpu_baseline": cpu,
-        }
-        line["sync_faults"] = sync_faults
-        if consistency is not None:
-            line["rank_consistency"] = consistency
-        if tail is not None:
-            line["eager_tail"] = tail
-        if alt:
-            line["alt_paths"] = alt
-        print(json.dumps(line), flush=True)
-    if dist_path:
-        dist.destroy_process_group()
+    cpu = None
+    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        cpu = cpu_baseline(B, args.cpu_seconds)
+    report(roofline, cpu, tail, consistency, alt)
 
 
 if __name__ == "__main__":

@@ -83,6 +83,10 @@ def draw(d, noise0=None):
 
 def oracle_grads(ndraw=NDRAW, pfiber=0.1, wvar=1.0, global_cls=None, noise0=None):
     """Per draw, the list of parameter gradients (None where autograd gave none)."""
+    # the process's thread count is put back afterwards: the fp32 oracle of the
+    # parity tests rounds differently on another count, and their bound moves
+    # with it (tests/test_gpu_parity.py: TOL_K x the fp32 oracle's error)
+    threads = torch.get_num_threads()
     torch.set_num_threads(min(8, os.cpu_count() or 1))
     orig = ref_gnn.GlobalModel
     if global_cls is not None:
@@ -91,19 +95,22 @@ def oracle_grads(ndraw=NDRAW, pfiber=0.1, wvar=1.0, global_cls=None, noise0=None
         m = ref_gnn.GNN(B=3, Fdim=10, T=12, F_s=1, F_t=2).double()
     finally:
         ref_gnn.GlobalModel = orig
-    m.load_state_dict(model_state())
-    m.train()
-    out_g = []
-    for d in range(ndraw):
-        ei, xs, xt, xe, u, uni = draw(d, noise0)
-        g = ref_gnn.Graph(ei, xs.double(), xt.double(), xe.double(), u.double())
-        m.zero_grad(set_to_none=True)
-        out = m(g)
-        loss, _ = loss_function(m, out.x_e, g.x_t, 1, 2000, 12, pclass=0.1, pfiber=pfiber, wvar=wvar,
-                                sharpness=SHARP, uniform=uni)
-        loss.backward()
-        out_g.append([None if p.grad is None else p.grad.detach().double().clone()
-                      for p in m.parameters()])
+    try:
+        m.load_state_dict(model_state())
+        m.train()
+        out_g = []
+        for d in range(ndraw):
+            ei, xs, xt, xe, u, uni = draw(d, noise0)
+            g = ref_gnn.Graph(ei, xs.double(), xt.double(), xe.double(), u.double())
+            m.zero_grad(set_to_none=True)
+            out = m(g)
+            loss, _ = loss_function(m, out.x_e, g.x_t, 1, 2000, 12, pclass=0.1, pfiber=pfiber,
+                                    wvar=wvar, sharpness=SHARP, uniform=uni)
+            loss.backward()
+            out_g.append([None if p.grad is None else p.grad.detach().double().clone()
+                          for p in m.parameters()])
+    finally:
+        torch.set_num_threads(threads)
     return out_g
 
 

@@ -145,8 +145,12 @@ def emu_pfsgnn():
 
 @pytest.mark.parametrize("capturable", [False, True])
 def test_resume_from_reference_adam_state(emu_pfsgnn, capturable):
+    threads = torch.get_num_threads()
     torch.set_num_threads(min(8, os.cpu_count() or 1))
-    wp, wm = check_resume(*run_resume(emu_pfsgnn, "cpu", capturable), max_ulp=2)
+    try:
+        wp, wm = check_resume(*run_resume(emu_pfsgnn, "cpu", capturable), max_ulp=2)
+    finally:
+        torch.set_num_threads(threads)    # (as tests/test_adam_pin.py:oracle_grads)
     print(f"capturable={capturable}: worst difference vs torch CPU Adam: parameters "
           f"{wp:.2f} ulp, moments {wm:.2f} ulp")
 

@@ -2,7 +2,7 @@
 # A/B of environment knobs on the bench step: ms/step and the edge kernels'
 # per-step times (roofline.kernel_ms_per_step), one bench process per setting.
 #   bash tools/env_ab.sh "" "PFSGNN_XCD_ORDER=0" ...      ("" = defaults)
-a=${AB_ARGS:-"--steps 30 --warmup 5 --no-cpu-baseline --alt-paths ,"}
+a=${AB_ARGS:-"--steps 30 --warmup 5 --full --no-cpu-baseline --alt-paths ,"}
 for v in "$@"; do
   env $v python bench.py $a 2>/dev/null | python3 -c "
 import json,sys

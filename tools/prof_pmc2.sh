@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp
 run() {
   name=$1; shift
   timeout -k 10 240 rocprofv3 --pmc "$@" --output-format csv -d "$root/$out/$name" -o run -- \
-    python3 "$root/bench.py" --steps 2 --warmup 1 --no-cpu-baseline > "$root/$out/$name.log" 2>&1
+    python3 "$root/bench.py" --steps 2 --warmup 1 --full --no-cpu-baseline > "$root/$out/$name.log" 2>&1
   rc=$?; echo "[pmc $name] rc=$rc"; return $rc
 }
 mkdir -p "$root/$out"

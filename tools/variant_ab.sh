@@ -2,7 +2,7 @@
 # A/B of tuning builds (tools/variants.sh) on the bench step: ms/step and the
 # edge kernels' per-step times (roofline.kernel_ms_per_step), default first.
 #   bash tools/variant_ab.sh name1 [name2 ...]
-a="--steps 30 --warmup 5 --no-cpu-baseline --alt-paths ,"
+a="--steps 30 --warmup 5 --full --no-cpu-baseline --alt-paths ,"
 for v in "" "$@"; do
   PFSGNN_LIB_VARIANT=$v python bench.py $a 2>/dev/null | python3 -c "
 import json,sys
