@@ -759,6 +759,44 @@ int pfsgnn_source_bwd_bn_msg(int G, int NF, int NC, int F, const float* y, const
                              float* dgamma, float* dbeta, float* g_xt,
                              const unsigned char* tmask, const float* msg, void* ws,
                              size_t ws_bytes, void* stream);
+/* The folded pair (complete graphs).  In training the engine wants no gxe
+ * from TModel's edge backward, and source_bwd, one launch later, reloads the
+ * same y rows and mask bytes and forms the same x and g_zt.  Where
+ * pfsgnn_tbwd_fold(F) is 1 on the current edge path (the MFMA paths at Fdim 8
+ * and 10; Fdim 16's source_bwd has no registers left for it),
+ *   pfsgnn_target_bwd_fold (pfsgnn_target_bwd_bn's arguments; bn_part and its
+ *     three inputs may all be NULL) with a mask and gxe == NULL runs a
+ *     mask-only kernel: it reads tmask (4 bytes per edge) and g_hsum only and
+ *     does NOT touch dWt1; GzT, g_xs and bn_part come out of the same
+ *     reduction as before;
+ *   pfsgnn_source_bwd_fold with dWt1 (tmask, Rs, Wt1, g_hsum required) also
+ *     accumulates dWt1[:,F:2F] += g_zt x^T.  gamma != NULL: the edge BatchNorm
+ *     coefficients as pfsgnn_source_bwd_bn (Sg / Sgx unused); gamma == NULL: Sg /
+ *     Sgx as pfsgnn_source_bwd.  msg: the message cache or NULL.
+ * Every output is bitwise that of pfsgnn_target_bwd_bn + pfsgnn_source_bwd_bn:
+ * the same operations in the same order, issued from the other kernel.  A
+ * caller gives pfsgnn_source_bwd_fold dWt1 exactly when the target call had a
+ * mask and no gxe.  Where pfsgnn_tbwd_fold(F) is 0, or the target call has no
+ * mask or wants gxe, both entry points run today's kernels (the target call
+ * then accumulates dWt1[:,F:2F] itself and the source call ignores dWt1). */
+int pfsgnn_tbwd_fold(int F);
+int pfsgnn_target_bwd_fold(int G, int NF, int NC, int F, const float* y, const float* sc,
+                           const float* sh, const float* Rs, const float* Wt1,
+                           const float* g_hsum, float* GzT, float* dWt1, float* gxe, float* g_xs,
+                           const unsigned char* tmask, const float* bn_Yp, const float* bn_mu,
+                           const float* bn_var, float bn_eps, float* bn_part, void* ws,
+                           size_t ws_bytes, void* stream);
+int pfsgnn_source_bwd_fold(int G, int NF, int NC, int F, const float* y, const float* sc,
+                           const float* sh, const float* Qt, const float* Ws1, const float* Ws2,
+                           const float* bs2, const float* mean, const float* coef,
+                           const float* Rs, const float* Wt1, const float* g_hsum,
+                           const float* g_next, const float* mu1, const float* inv1,
+                           const float* var1, const float* gamma, long long n, float eps,
+                           float* g_tot, float* GzS, float* dWs1, float* dWs2, float* dbs2,
+                           float* Sg, float* Sgx, float* alpha, float* gam0, float* gam1,
+                           float* dgamma, float* dbeta, float* g_xt, const unsigned char* tmask,
+                           const float* msg, float* dWt1, void* ws, size_t ws_bytes,
+                           void* stream);
 /* Sg = sum g, Sgx = sum g*(y-mu1)*inv1 (standalone EdgeModel backward). */
 int pfsgnn_edge_bn_grad_sums(int G, int NF, int NC, int F, const float* g, const float* y,
                              const float* mu1, const float* inv1, float* Sg, float* Sgx,

@@ -1609,7 +1609,7 @@ size_t edge_ws_floats(const EdgeGeo& geo, int G, int NC, int F) {
   edge = std::max(edge, ks * 4 * C * NS + C * NS + 1024);                           // source fwd
   edge = std::max(edge, colp * C + 1024);                                           // target fwd
   edge = std::max(edge, nb * C * F + ks * C * NS + 1024);                           // target bwd
-  edge = std::max(edge, nb * (C * (C + 1) + C * F + 2 * F) + colp * C + 4096);      // source bwd
+  edge = std::max(edge, nb * (C * (C + 1) + 2 * C * F + 2 * F) + colp * C + 4096);  // source bwd (+ dWt1 folded)
   edge = std::max(edge, nb * (F * (H + 1) + H * F) + colp * H + ks * H * NS + 4096);  // edge bwd
   edge = std::max(edge, colp * 4 + ks * NS + nb * (F * (F + 1) + F + 1) + 4096);   // loss
   edge += (size_t)geo.NT * (H + 2 * C) + 4 * H * H + 8 * 256;
@@ -1963,7 +1963,9 @@ static int target_bwd_impl(const pfsgnn_sliced_t* sl, int G, int NF, int NC, int
                            const float* Wt1, const float* g_hsum, float* GzT, float* dWt1,
                            float* gxe, float* g_xs, const unsigned char* tmask, void* ws,
                            size_t ws_bytes, void* stream,
-                           const FiberBnSums& bs = FiberBnSums{}) {
+                           const FiberBnSums& bs = FiberBnSums{}, bool fold = false) {
+  // fold (pfsgnn_target_bwd_fold): the mask-only kernel, no weight-gradient
+  // partial and no reduction into dWt1 -- source_bwd takes dWt1[:, F:2F]
   if (int rc = check_dims("pfsgnn_target_bwd", G, NF, NC, F)) return rc;
   if (int rc = check_sliced("pfsgnn_target_bwd", sl, NC, F)) return rc;
   PF_REQUIRE(y && Rs && Wt1 && g_hsum && GzT && dWt1, "pfsgnn_target_bwd", "null");
@@ -1971,13 +1973,13 @@ static int target_bwd_impl(const pfsgnn_sliced_t* sl, int G, int NF, int NC, int
   const int C = 2 * F;
   Ws w{reinterpret_cast<char*>(ws), ws_bytes};
   hipStream_t st = as_stream(stream);
-  float* part = pf::defer_take((size_t)geo.nblocks * C * F);
+  float* part = fold ? nullptr : pf::defer_take((size_t)geo.nblocks * C * F);
   const bool defer = part != nullptr;
-  if (!defer) part = w.take((size_t)geo.nblocks * C * F);
+  if (!defer && !fold) part = w.take((size_t)geo.nblocks * C * F);
   float* gz = fiber_dst(geo, C, GzT, w);
   const float* ghT = (sl || use_mfma()) ? g_hsum
                                        : class_rows(g_hsum, C, geo, w, st);
-  PF_REQUIRE(part && gz && ghT, "pfsgnn_target_bwd", "workspace too small");
+  PF_REQUIRE((part || fold) && gz && ghT, "pfsgnn_target_bwd", "workspace too small");
   { pf::Timer tm_("target_bwd", st);
   if (sl) {
     float* tabs = w.take((size_t)pfm::sl_tab_floats(geo, F));
@@ -2000,9 +2002,11 @@ static int target_bwd_impl(const pfsgnn_sliced_t* sl, int G, int NF, int NC, int
                                                            geo.NS),
                                 no_lin(), st, bs))
     return rc;
-  const RedDesc rd{part, geo.nblocks, (size_t)C * F, F, C, F, dWt1 + F, C, 1, 1.f};
-  if (defer) pf::defer_push(&rd, 1);
-  else launch_reduce_multi(&rd, 1, st);
+  if (!fold) {
+    const RedDesc rd{part, geo.nblocks, (size_t)C * F, F, C, F, dWt1 + F, C, 1, 1.f};
+    if (defer) pf::defer_push(&rd, 1);
+    else launch_reduce_multi(&rd, 1, st);
+  }
   return pf::check_launch("pfsgnn_target_bwd");
 }
 
@@ -2026,6 +2030,28 @@ extern "C" int pfsgnn_target_bwd_bn(int G, int NF, int NC, int F, const float* y
   return target_bwd_impl(nullptr, G, NF, NC, F, y, sc, sh, Rs, Wt1, g_hsum, GzT, dWt1, gxe, g_xs,
                          tmask, ws, ws_bytes, stream,
                          FiberBnSums{bn_Yp, bn_mu, bn_var, bn_eps, bn_part});
+}
+
+// The folded pair (include/pfsgnn.h): where the edge path's source_bwd also
+// takes TModel's edge weight gradient (pfm::source_bwd_folds), target_bwd with
+// the forward's mask and no edge-input gradient runs its mask-only form
+// (km_target_bwd's NW) and leaves dWt1[:, F:2F] to pfsgnn_source_bwd_fold.
+static bool tbwd_folds(int F) { return use_mfma() && pfm::source_bwd_folds(F, mf_prec(1, F)); }
+
+extern "C" int pfsgnn_tbwd_fold(int F) { return tbwd_folds(F) ? 1 : 0; }
+
+extern "C" int pfsgnn_target_bwd_fold(int G, int NF, int NC, int F, const float* y,
+                                      const float* sc, const float* sh, const float* Rs,
+                                      const float* Wt1, const float* g_hsum, float* GzT,
+                                      float* dWt1, float* gxe, float* g_xs,
+                                      const unsigned char* tmask, const float* bn_Yp,
+                                      const float* bn_mu, const float* bn_var, float bn_eps,
+                                      float* bn_part, void* ws, size_t ws_bytes, void* stream) {
+  PF_REQUIRE(!bn_part || (g_xs && bn_Yp && bn_mu && bn_var), "pfsgnn_target_bwd_fold",
+             "BatchNorm sums need g_xs, Yp, mu, var");
+  const FiberBnSums bs = bn_part ? FiberBnSums{bn_Yp, bn_mu, bn_var, bn_eps, bn_part} : FiberBnSums{};
+  return target_bwd_impl(nullptr, G, NF, NC, F, y, sc, sh, Rs, Wt1, g_hsum, GzT, dWt1, gxe, g_xs,
+                         tmask, ws, ws_bytes, stream, bs, tmask && !gxe && tbwd_folds(F));
 }
 
 extern "C" int pfsgnn_sl_target_bwd(const pfsgnn_sliced_t* sl, int G, int NF, int NC, int F,
@@ -2118,7 +2144,7 @@ static int source_bwd_impl(const pfsgnn_sliced_t* sl, int G, int NF, int NC, int
                            const float* inv1, float* g_tot, float* GzS, float* dWs1, float* dWs2,
                            float* dbs2, float* Sg, float* Sgx, const Bn2Bwd* bb, float* g_xt,
                            const unsigned char* tmask, void* ws, size_t ws_bytes, void* stream,
-                           const float* msg = nullptr);
+                           const float* msg = nullptr, float* dWt1f = nullptr);
 
 extern "C" int pfsgnn_source_bwd(int G, int NF, int NC, int F, const float* y, const float* sc,
                                  const float* sh, const float* Qt, const float* Ws1,
@@ -2186,6 +2212,29 @@ extern "C" int pfsgnn_source_bwd_bn_msg(
                          &bb, g_xt, tmask, ws, ws_bytes, stream, msg);
 }
 
+extern "C" int pfsgnn_source_bwd_fold(
+    int G, int NF, int NC, int F, const float* y, const float* sc, const float* sh,
+    const float* Qt, const float* Ws1, const float* Ws2, const float* bs2, const float* mean,
+    const float* coef, const float* Rs, const float* Wt1, const float* g_hsum,
+    const float* g_next, const float* mu1, const float* inv1, const float* var1,
+    const float* gamma, long long n, float eps, float* g_tot, float* GzS, float* dWs1,
+    float* dWs2, float* dbs2, float* Sg, float* Sgx, float* alpha, float* gam0, float* gam1,
+    float* dgamma, float* dbeta, float* g_xt, const unsigned char* tmask, const float* msg,
+    float* dWt1, void* ws, size_t ws_bytes, void* stream) {
+  const char* where = "pfsgnn_source_bwd_fold";
+  PF_REQUIRE(dWt1 && tmask && Rs, where, "the folded pair needs dWt1, tmask and TModel's part");
+  if (!gamma)   // the BatchNorm sums only (pfsgnn_source_bwd / _msg)
+    return source_bwd_impl(nullptr, G, NF, NC, F, y, sc, sh, Qt, Ws1, Ws2, bs2, mean, coef, Rs,
+                           Wt1, g_hsum, g_next, mu1, inv1, g_tot, GzS, dWs1, dWs2, dbs2, Sg, Sgx,
+                           nullptr, g_xt, tmask, ws, ws_bytes, stream, msg, dWt1);
+  PF_REQUIRE(mu1 && inv1 && var1 && n > 0 && alpha && gam0 && gam1 && dgamma && dbeta, where,
+             "null");
+  const Bn2Bwd bb{gamma, mu1, var1, n, eps, alpha, gam0, gam1, dgamma, dbeta};
+  return source_bwd_impl(nullptr, G, NF, NC, F, y, sc, sh, Qt, Ws1, Ws2, bs2, mean, coef, Rs, Wt1,
+                         g_hsum, g_next, mu1, inv1, g_tot, GzS, dWs1, dWs2, dbs2, nullptr, nullptr,
+                         &bb, g_xt, tmask, ws, ws_bytes, stream, msg, dWt1);
+}
+
 extern "C" int pfsgnn_sl_source_bwd(const pfsgnn_sliced_t* sl, int G, int NF, int NC, int F,
                                     const float* y, const float* sc, const float* sh,
                                     const float* Qt, const float* Ws1, const float* Ws2,
@@ -2227,7 +2276,7 @@ static int source_bwd_impl(const pfsgnn_sliced_t* sl, int G, int NF, int NC, int
                            const float* inv1, float* g_tot, float* GzS, float* dWs1, float* dWs2,
                            float* dbs2, float* Sg, float* Sgx, const Bn2Bwd* bb, float* g_xt,
                            const unsigned char* tmask, void* ws, size_t ws_bytes, void* stream,
-                           const float* msg) {
+                           const float* msg, float* dWt1f) {
   if (int rc = check_dims("pfsgnn_source_bwd", G, NF, NC, F)) return rc;
   PF_REQUIRE(!msg || (!sl && msg_bytes(G, NF, NC, F) > 0), "pfsgnn_source_bwd_msg",
              "the message cache is not kept on this path (pfsgnn_msg_bytes is 0)");
@@ -2242,10 +2291,15 @@ static int source_bwd_impl(const pfsgnn_sliced_t* sl, int G, int NF, int NC, int
   const int C = 2 * F;
   const size_t nb = geo.nblocks;
   Ws w{reinterpret_cast<char*>(ws), ws_bytes};
-  float* pW2 = pf::defer_take(nb * C * (C + 1) + nb * C * F);
+  // (dWt1f: TModel's edge weight gradient dWt1[:, F:2F] from this kernel too,
+  // the other half of pfsgnn_target_bwd_fold's mask-only form)
+  const bool fold = dWt1f && tmask && Rs && !sl && tbwd_folds(F);
+  const size_t nW = nb * C * (C + 1) + nb * C * F * (fold ? 2 : 1);
+  float* pW2 = pf::defer_take(nW);
   const bool defer = pW2 != nullptr;
-  if (!defer) pW2 = w.take(nb * C * (C + 1) + nb * C * F);
+  if (!defer) pW2 = w.take(nW);
   float* pW1 = pW2 ? pW2 + nb * C * (C + 1) : nullptr;
+  float* pWt = fold && pW1 ? pW1 + nb * C * F : nullptr;
   float* pCol = w.take((size_t)G * col_bpg(geo, sl) * NC * C);
   float* pBN = w.take(nb * 2 * F);
   hipStream_t st = as_stream(stream);
@@ -2266,7 +2320,7 @@ static int source_bwd_impl(const pfsgnn_sliced_t* sl, int G, int NF, int NC, int
     for (int rep = 0, nrep = 1 + pf::repeats("source_bwd"); rep < nrep; ++rep)
       if (int rc = pfm::source_bwd(geo, F, msg, y, sc, sh, QtT, Ws1, Ws2, bs2, mean, coef, Rs, Wt1,
                                    ghT, g_next, mu1, inv1, g_tot, pW2, pW1, pCol, pBN, tmask,
-                                   mf_prec(1, F), st))
+                                   mf_prec(1, F), st, pWt))
         return rc;
   } else {
   DISPATCH_F(F, hipLaunchKernelGGL(k_source_bwd<FF>, dim3(edge_grid(geo)), dim3(256), 0, st, geo, y,
@@ -2275,19 +2329,21 @@ static int source_bwd_impl(const pfsgnn_sliced_t* sl, int G, int NF, int NC, int
   }
   tm_.end(); }
   {
-    RedDesc rd[5] = {{pBN, (int)nb, (size_t)2 * F, F, 1, F, Sg, F, 0, 1.f},
+    RedDesc rd[6] = {{pBN, (int)nb, (size_t)2 * F, F, 1, F, Sg, F, 0, 1.f},
                      {pBN + F, (int)nb, (size_t)2 * F, F, 1, F, Sgx, F, 0, 1.f},
                      {pW2, (int)nb, (size_t)C * (C + 1), C + 1, C, C, dWs2, C, 1, 1.f},
                      {pW2 + C, (int)nb, (size_t)C * (C + 1), C + 1, C, 1, dbs2, 1, 1, 1.f},
-                     {pW1, (int)nb, (size_t)C * F, F, C, F, dWs1 + F, C, 1, 1.f}};
+                     {pW1, (int)nb, (size_t)C * F, F, C, F, dWs1 + F, C, 1, 1.f},
+                     {pWt, (int)nb, (size_t)C * F, F, C, F, fold ? dWt1f + F : nullptr, C, 1, 1.f}};
+    const int nw = fold ? 4 : 3;   // weight-gradient reductions
     // the BatchNorm sums are read at once (bn2_bwd_coef); the weight
     // gradients only by the optimizer
     const bool sums = mu1 && !bb;   // BN sums by the generic reduce
     const RedDesc* now = sums ? rd : rd + 2;
-    int nnow = sums ? 5 : 3;
+    int nnow = (sums ? 2 : 0) + nw;
     if (defer) {
-      pf::defer_push(rd + 2, 3);
-      nnow -= 3;
+      pf::defer_push(rd + 2, nw);
+      nnow -= nw;
     }
     if (nnow) launch_reduce_multi(now, nnow, st);
   }

@@ -49,7 +49,12 @@ int source_bwd(const EdgeGeo& geo, int F, const float* msg, const float* y, cons
                const float* bs2, const float* mean, const float* coef, const float* Rs,
                const float* Wt1, const float* ghS, const float* g_next, const float* mu1,
                const float* inv1, float* g_tot, float* pW2, float* pW1, float* pCol, float* pBN,
-               const uint8_t* tmask, int prec, hipStream_t st);
+               const uint8_t* tmask, int prec, hipStream_t st, float* pWt = nullptr);
+// pWt (optional; needs tmask and Rs): source_bwd also writes TModel's edge
+// weight-gradient block partials [nblocks][2F][F] (target_bwd's partW), so that
+// target_bwd can run its mask-only form; source_bwd_folds: whether the
+// (Fdim, precision) pair has that form
+bool source_bwd_folds(int F, int prec);
 int edge_mlp_bwd(const EdgeGeo& geo, int F, const float* g_tot, const float* alpha,
                  const float* gam0, const float* gam1, const float* y, const float* xe,
                  const float* xsc, const float* xsh, const float* Ps, const float* PtS,

@@ -709,7 +709,11 @@ __global__ __launch_bounds__(256) void km_target_fwd(EdgeGeo geo, const float* _
 // ============================================================ TModel bwd
 // g_z = g_hsum[c] * lrelu'(z) per edge; per-fiber sums of g_z (-> g_Rs), the
 // edge-input gradient Wt1[:, F:2F]^T g_z (optional) and dWt1[:, F:2F] += g_z x^T.
-template <int F, int PREC, bool TM>
+// NW (with TM, no gxe): no weight gradient -- km_source_bwd takes it (TW) -- so
+// only the per-fiber sums are left, which need the mask byte and g_hsum alone:
+// no y row, no x, no split, no image, no MFMA, no block partial.  The sums are
+// the same operations in the same order on the same grid as without NW.
+template <int F, int PREC, bool TM, bool NW = false>
 __global__ __launch_bounds__(256) void km_target_bwd(EdgeGeo geo, const float* __restrict__ y,
                                                      const float* __restrict__ sc,
                                                      const float* __restrict__ sh,
@@ -721,11 +725,12 @@ __global__ __launch_bounds__(256) void km_target_bwd(EdgeGeo geo, const float* _
                                                      float* __restrict__ partW,
                                                      const uint8_t* __restrict__ tmask) {
   constexpr int C = 2 * F, NT = GM<C>::NT;
+  static_assert(!NW || TM, "the mask-only form reads the mask");
   constexpr int NIMG = NT + 1;  // g_z tiles | x
   using WI = WgImg<PREC>;       // weight-gradient images: bf16x3, or exact fp32 at PREC 0
   MF_GEO
-  __shared__ __attribute__((aligned(16))) short imgs[4 * NIMG * WI::U];
-  __shared__ float scratch[4 * C * F];
+  __shared__ __attribute__((aligned(16))) short imgs[NW ? 4 : 4 * NIMG * WI::U];
+  __shared__ float scratch[NW ? 1 : 4 * C * F];
   __shared__ __attribute__((aligned(16))) float ghl[MF_MAX_CPS * ClassRows<C>::CP];
   ClassRows<C>::stage(ghl, ghS, geo.NT, (long long)gg * geo.NC + c0, c1 - c0);
   short* img = imgs + wave * NIMG * WI::U;
@@ -734,7 +739,7 @@ __global__ __launch_bounds__(256) void km_target_bwd(EdgeGeo geo, const float* _
   FwdLayer<FP(PREC), C, F> L1;
   if constexpr (!TM) L1.load([&](int h, int k) { return Wt1[h * 2 * F + F + k]; }, lane);
   GradLayer<PREC, F, C> LT;
-  LT.load([&](int k, int h) { return gxe ? Wt1[h * 2 * F + F + k] : 0.f; }, lane);
+  if constexpr (!NW) LT.load([&](int k, int h) { return gxe ? Wt1[h * 2 * F + F + k] : 0.f; }, lane);
   floatx4 rs[NT], accF[NT], accW[NT];
 #pragma unroll
   for (int tt = 0; tt < NT; ++tt) {
@@ -750,12 +755,12 @@ __global__ __launch_bounds__(256) void km_target_bwd(EdgeGeo geo, const float* _
   auto load = [&](int c) {
     Rows<1> r;
     const uint32_t co = (uint32_t)c * eoc;
-    r.v[0] = ld_frows<F>(ry, co, ro);
+    if constexpr (NW) r.v[0] = zero4(); else r.v[0] = ld_frows<F>(ry, co, ro);
     if constexpr (TM) r.m = __builtin_amdgcn_raw_buffer_load_b8(rtm, eo0 + g4, co, 0);
     return r;
   };
-  class_stream<MF_DEPTH_BWD>(c0, c1, load, [&](const Rows<1>& rows, int c) {
-    const floatx4 x[1] = {edge_in<F>(rows.v[0], fm, sc, scv, shv)};
+  class_stream<NW ? 2 * MF_DEPTH_BWD : MF_DEPTH_BWD>(c0, c1, load, [&](const Rows<1>& rows, int c) {
+    [[maybe_unused]] const floatx4 x[1] = {edge_in<F>(rows.v[0], fm, sc, scv, shv)};
     floatx4 z[NT], gz[NT];
     if constexpr (!TM) {
 #pragma unroll
@@ -773,6 +778,7 @@ __global__ __launch_bounds__(256) void km_target_bwd(EdgeGeo geo, const float* _
       }
       accF[tt] += gz[tt];
     }
+    if constexpr (NW) return;
     Fr sgz[NT];
 #pragma unroll
     for (int tt = 0; tt < NT; ++tt) sgz[tt] = split(gz[tt]);
@@ -800,10 +806,11 @@ __global__ __launch_bounds__(256) void km_target_bwd(EdgeGeo geo, const float* _
         if (h >= 0) GzT[(size_t)ks * C * NS + (size_t)h * NS + n] = accF[tt][r];
       }
   }
-  block_partial(accW, scratch, C * F, [&](int a, int s, int jj) {
-    const int h = GM<C>::mrow(a, s), k = GM<F>::mrow(0, jj);
-    return (h >= 0 && k >= 0) ? h * F + k : -1;
-  }, partW + (size_t)bx * C * F);
+  if constexpr (!NW)
+    block_partial(accW, scratch, C * F, [&](int a, int s, int jj) {
+      const int h = GM<C>::mrow(a, s), k = GM<F>::mrow(0, jj);
+      return (h >= 0 && k >= 0) ? h * F + k : -1;
+    }, partW + (size_t)bx * C * F);
 }
 
 // ============================================================ SModel bwd (+T, +BN sums)
@@ -817,7 +824,21 @@ __global__ __launch_bounds__(256) void km_target_bwd(EdgeGeo geo, const float* _
 // the same values bit for bit (the cache holds what the forward computed), 10
 // fewer fp32 MFMAs per class and that layer's dependent chain off the class's
 // critical path, for 80 B per edge written in the forward and read here.
-template <int F, int PREC, bool TM, bool MSG = false>
+// TW (with TM and TModel's part): the kernel also takes TModel's edge weight
+// gradient dWt1[:, F:2F] += g_zt x^T (partWt, block partials shaped like
+// km_target_bwd's partW): it already forms g_zt and its split for the input
+// gradient and holds x in a weight-gradient image, so the fold costs one more
+// image and two more outer-product tiles per class at Fdim 10 (PACK: g_zt's
+// tile-1 row rides in R3's free slot 2, its tile 0 is a sixth image R4), NT
+// images and tiles otherwise -- and target_bwd shrinks to its mask-only form
+// (km_target_bwd's NW).  The results are BITWISE km_target_bwd's: the same
+// operands on the same grid, and the same three-product form (WI::mma), which
+// is why the tile-1 row does not reuse the four-product R3 C2 tile (MF_WG4) of
+// dWs1 but takes a three-product R3 C2 of its own.  A training step is
+// chaotic enough (Adam on gradients that are rounding noise, 1 / std^4
+// features) that sums in another order change the parameters visibly within
+// a few steps.
+template <int F, int PREC, bool TM, bool MSG = false, bool TW = false>
 __global__ __launch_bounds__(256, 2) void km_source_bwd(
     EdgeGeo geo, const float* __restrict__ msg, const float* __restrict__ y, const float* __restrict__ sc,
     const float* __restrict__ sh, const float* __restrict__ QtS, const float* __restrict__ Ws1,
@@ -826,7 +847,9 @@ __global__ __launch_bounds__(256, 2) void km_source_bwd(
     const float* __restrict__ ghS, const float* __restrict__ g_next,
     const float* __restrict__ mu1, const float* __restrict__ inv1, float* __restrict__ g_tot,
     float* __restrict__ partW2, float* __restrict__ partW1, float* __restrict__ partCol,
-    float* __restrict__ partBN, const uint8_t* __restrict__ tmask) {
+    float* __restrict__ partBN, const uint8_t* __restrict__ tmask,
+    float* __restrict__ partWt) {
+  static_assert(!TW || TM, "the folded TModel weight gradient reads the mask");
   constexpr int C = 2 * F, NT = GM<C>::NT;
   // PACK (Fdim 10: C = 20 messages, 2 tiles of which the second holds ONE row
   // per lane group; x has 3 rows per group): the weight-gradient operands are
@@ -837,7 +860,8 @@ __global__ __launch_bounds__(256, 2) void km_source_bwd(
   // padding rows of one operand carrying the other's live rows.  Every output
   // element is the same products in the same order: bitwise the unpacked sums.
   constexpr bool PACK = MF_SB_PACK && NT == 2 && GM<C>::nreg(1) == 1 && GM<F>::NT == 1 && GM<F>::RPG == 3;
-  constexpr int NIMG = PACK ? 5 : 3 * NT + 1;   // g_m | a | g_zs | x (packed: R1 R2 R3 C1 C2)
+  // g_m | a | g_zs | x (packed: R1 R2 R3 C1 C2); TW: + g_zt (packed: + R4)
+  constexpr int NIMG = (PACK ? 5 : 3 * NT + 1) + (TW ? (PACK ? 1 : NT) : 0);
   constexpr int SCR = C * (C + 1) > C * F ? C * (C + 1) : C * F;
   using WI = WgImg<PREC>;
   MF_GEO
@@ -859,7 +883,10 @@ __global__ __launch_bounds__(256, 2) void km_source_bwd(
   short* im_r3 = img + 2 * WI::U;
   short* im_c1 = img + 3 * WI::U;
   short* im_c2 = img + 4 * WI::U;
-  (void)im_r1; (void)im_r2; (void)im_r3; (void)im_c1; (void)im_c2;
+  // (TW) g_zt: R4 = its tile 0 (PACK), or its NT tiles behind x
+  short* im_r4 = img + 5 * WI::U;
+  short* im_zt = im_x + WI::U;
+  (void)im_r1; (void)im_r2; (void)im_r3; (void)im_c1; (void)im_c2; (void)im_r4; (void)im_zt;
   const long long CNS = (long long)C * NS;
   const bool tpart = Rs != nullptr;
 
@@ -908,7 +935,11 @@ __global__ __launch_bounds__(256, 2) void km_source_bwd(
   [[maybe_unused]] const RowOff<C> roC(eo0, RB, g4);
 
   floatx4 accW2[NT * NT], accW1[NT], accB[NT];
-  floatx4 accP[5];   // (PACK) R1 C1, R1 C2, R2 C2, R3 C1, R3 C2
+  constexpr int NP = TW ? 7 : 5, NPI = TW ? 6 : 5;   // tiles, images
+  // (PACK) R1 C1, R1 C2, R2 C2, R3 C1, R3 C2 (TW: + R4 C2 and R3 C2 again, both
+  // in km_target_bwd's three-product form)
+  floatx4 accP[NP];
+  [[maybe_unused]] floatx4 accWt[NT];   // (TW, unpacked) g_zt x^T
 #pragma unroll
   for (int tt = 0; tt < NT; ++tt) {
     accW1[tt] = zero4();
@@ -917,7 +948,9 @@ __global__ __launch_bounds__(256, 2) void km_source_bwd(
     for (int nb = 0; nb < NT; ++nb) accW2[tt * NT + nb] = zero4();
   }
 #pragma unroll
-  for (int i = 0; i < 5; ++i) accP[i] = zero4();
+  for (int i = 0; i < NP; ++i) accP[i] = zero4();
+#pragma unroll
+  for (int tt = 0; tt < NT; ++tt) accWt[tt] = zero4();
   floatx4 sg = zero4(), sgx = zero4();
   const s16x8 ones = ones_reg();
   __syncthreads();   // qtl, ghl
@@ -981,6 +1014,20 @@ __global__ __launch_bounds__(256, 2) void km_source_bwd(
       for (int r = 0; r < GM<C>::nreg(tt); ++r) gz[tt][r] *= dlrelu(zs[tt][r]);
       sgz[tt] = split(gz[tt]);
     }
+    // (TW) TModel's g_z = g_hsum[c] * slope(mask) and its split, ahead of the
+    // image writes: they feed an image as well as the input gradient below
+    [[maybe_unused]] floatx4 ztw[NT];
+    [[maybe_unused]] Fr sztw[NT];
+    if constexpr (TW) {
+#pragma unroll
+      for (int tt = 0; tt < NT; ++tt) {
+        const floatx4 gh = ClassRows<C>::get(ghl, c - c0, tt, g4);
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          ztw[tt][r] = (fvalid && r < GM<C>::nreg(tt)) ? gh[r] * mask_slope(rows.m, 4 * tt + r) : 0.f;
+        sztw[tt] = split(ztw[tt]);
+      }
+    }
     // the weight-gradient images are written first: their LDS latency hides
     // behind the input-gradient chains below
     lds_order();
@@ -988,7 +1035,13 @@ __global__ __launch_bounds__(256, 2) void km_source_bwd(
     if constexpr (PACK) {
       r3v = floatx4{gm[1][0], gz[1][0], 0.f, 0.f};
       c2v = floatx4{as[1][0], x[0][0], x[0][1], x[0][2]};
-      const Fr sr3 = {s16x4{sgm[1].h[0], sgz[1].h[0], 0, 0}, s16x4{sgm[1].l[0], sgz[1].l[0], 0, 0}};
+      Fr sr3 = {s16x4{sgm[1].h[0], sgz[1].h[0], 0, 0}, s16x4{sgm[1].l[0], sgz[1].l[0], 0, 0}};
+      if constexpr (TW) {   // R3's slot 2: g_zt's tile-1 row; R4: its tile 0
+        r3v[2] = ztw[1][0];
+        sr3.h[2] = sztw[1].h[0];
+        sr3.l[2] = sztw[1].l[0];
+        WI::put(im_r4, lane, ztw[0], sztw[0]);
+      }
       WI::put(im_r1, lane, gm[0], sgm[0]);
       WI::put(im_r2, lane, gz[0], sgz[0]);
       WI::put(im_r3, lane, r3v, sr3);
@@ -1002,15 +1055,20 @@ __global__ __launch_bounds__(256, 2) void km_source_bwd(
         WI::put(im_gz + tt * WI::U, lane, gz[tt], sgz[tt]);
       }
       WI::put(im_x, lane, x[0], split(x[0]));
+      if constexpr (TW) {
+#pragma unroll
+        for (int tt = 0; tt < NT; ++tt) WI::put(im_zt + tt * WI::U, lane, ztw[tt], sztw[tt]);
+      }
     }
     lds_order();
 #if MF_WG_EARLY_READS
     // the transposed image reads go out now, ahead of the input-gradient
     // chains (as in km_edge_mlp_bwd)
-    typename WI::R rx, ra[NT], rgm[NT], rgz[NT], rp[5], rq[2];
+    typename WI::R rx, ra[NT], rgm[NT], rgz[NT], rp[NPI], rq[2];
+    [[maybe_unused]] typename WI::R rzt[NT];
     if constexpr (PACK) {
 #pragma unroll
-      for (int i = 0; i < 5; ++i) rp[i] = WI::rd(img + i * WI::U, lane);
+      for (int i = 0; i < NPI; ++i) rp[i] = WI::rd(img + i * WI::U, lane);
 #if MF_WG4
       lds_order();   // (the B images' second reads: mma4)
       rq[0] = WI::rd(im_c1, lane);
@@ -1023,13 +1081,16 @@ __global__ __launch_bounds__(256, 2) void km_source_bwd(
         ra[tt] = WI::rd(im_a + tt * WI::U, lane);
         rgm[tt] = WI::rd(im_gm + tt * WI::U, lane);
         rgz[tt] = WI::rd(im_gz + tt * WI::U, lane);
+        if constexpr (TW) rzt[tt] = WI::rd(im_zt + tt * WI::U, lane);
       }
     }
     lds_order();
 #endif
     floatx4 g[1] = {zero4()};
     if constexpr (PREC >= 1) L1sT.apply(sgz, g); else L1sT.apply(gz, g);
-    if (tpart) {  // TModel's per-edge input gradient (gnn.py:188-190)
+    if constexpr (TW) {   // TModel's per-edge input gradient from the early g_zt
+      if constexpr (PREC >= 1) L1tT.apply(sztw, g); else L1tT.apply(ztw, g);
+    } else if (tpart) {  // TModel's per-edge input gradient (gnn.py:188-190)
       floatx4 zt[NT];
       if constexpr (!TM) {   // its pre-activation recomputed
 #pragma unroll
@@ -1079,6 +1140,11 @@ __global__ __launch_bounds__(256, 2) void km_source_bwd(
       accP[2] = WI::mma4(t2, tc2, accP[2]);
       accP[3] = WI::mma4(t3, tc1, accP[3]);
       accP[4] = WI::mma4(t3, tc2, accP[4]);
+      if constexpr (TW) {   // km_target_bwd's three-product form, its operands
+        const typename WI::TB tx3 = WI::B(rp[4]);
+        accP[5] = WI::mma(WI::A(rp[5]), tx3, accP[5]);
+        accP[6] = WI::mma(t3, tx3, accP[6]);
+      }
 #else
       const typename WI::TB tc1 = WI::B(rp[3]), tc2 = WI::B(rp[4]);
       accP[0] = WI::mma(t1, tc1, accP[0]);
@@ -1086,6 +1152,10 @@ __global__ __launch_bounds__(256, 2) void km_source_bwd(
       accP[2] = WI::mma(t2, tc2, accP[2]);
       accP[3] = WI::mma(t3, tc1, accP[3]);
       accP[4] = WI::mma(t3, tc2, accP[4]);
+      if constexpr (TW) {
+        accP[5] = WI::mma(WI::A(rp[5]), tc2, accP[5]);
+        accP[6] = WI::mma(t3, tc2, accP[6]);
+      }
 #endif
       // per-class sums of g_zs: R2's rows, and R3's register slot 1
       const floatx4 cs2 = WI::colsum(t2, gz[0], ones), cs3 = WI::colsum(t3, r3v, ones);
@@ -1124,6 +1194,13 @@ __global__ __launch_bounds__(256, 2) void km_source_bwd(
       const typename WI::TA tgz = WI::A(im_gz + tt * WI::U, lane);
 #endif
       accW1[tt] = WI::mma(tgz, tx, accW1[tt]);
+      if constexpr (TW) {
+#if MF_WG_EARLY_READS
+        accWt[tt] = WI::mma(WI::A(rzt[tt]), tx, accWt[tt]);
+#else
+        accWt[tt] = WI::mma(WI::A(im_zt + tt * WI::U, lane), tx, accWt[tt]);
+#endif
+      }
       const floatx4 cs = WI::colsum(tgz, gz[tt]);
       if (j16 == WI::CS_LANE) {
 #pragma unroll
@@ -1190,6 +1267,24 @@ __global__ __launch_bounds__(256, 2) void km_source_bwd(
       const int h = GM<C>::mrow(a, s), k = GM<F>::mrow(0, jj);
       return (h >= 0 && k >= 0) ? h * F + k : -1;
     }, partW1 + (size_t)bx * C * F);
+  }
+  if constexpr (TW) {
+    if constexpr (PACK) {
+      // dWt1[:, F:2F] [h][k]: R4 C2 (tile-0 rows x C2's slots 1-3 = x) and the
+      // three-product R3 C2 (R3's slot 2 = the tile-1 row of g_zt)
+      block_partial(accP, scratch, C * F, [&](int a, int s, int jj) {
+        int h = -1, k = -1;
+        if ((jj & 3) != 0) k = GM<F>::row(jj >> 2, (jj & 3) - 1);
+        if (a == 5) h = GM<C>::mrow(0, s);
+        if (a == 6 && (s & 3) == 2) h = GM<C>::row(s >> 2, 4);
+        return (h >= 0 && k >= 0) ? h * F + k : -1;
+      }, partWt + (size_t)bx * C * F);
+    } else {
+      block_partial(accWt, scratch, C * F, [&](int a, int s, int jj) {
+        const int h = GM<C>::mrow(a, s), k = GM<F>::mrow(0, jj);
+        return (h >= 0 && k >= 0) ? h * F + k : -1;
+      }, partWt + (size_t)bx * C * F);
+    }
   }
   if (mu1) {
     __syncthreads();
@@ -1546,7 +1641,21 @@ int target_fwd(const EdgeGeo& geo, int F, const float* y, const float* sc, const
 int target_bwd(const EdgeGeo& geo, int F, const float* y, const float* sc, const float* sh,
                const float* Rs, const float* Wt1, const float* ghS, float* gz, float* gxe,
                float* part, const uint8_t* tmask, int prec, hipStream_t st) {
-  if (tmask) {
+  if (!part) {   // the mask-only form (NW): the weight gradient is source_bwd's (TW)
+    if (!tmask || gxe || !source_bwd_folds(F, prec))
+      return pf::fail("pfsgnn mfma", "target_bwd: no mask-only form for this call");
+#define MF_CASE_NW(FF, PP)                                                                      \
+  case FF * 8 + PP:                                                                             \
+    hipLaunchKernelGGL((km_target_bwd<FF, PP, true, true>), dim3(edge_grid(geo)), dim3(256), 0, \
+                       st, geo, y, sc, sh, Rs, Wt1, ghS, gz, gxe, part, tmask);                 \
+    break;
+    switch (F * 8 + prec) {
+      MF_CASE_NW(8, 0) MF_CASE_NW(8, 1) MF_CASE_NW(10, 0) MF_CASE_NW(10, 1) MF_CASE_NW(10, 2)
+      MF_CASE_NW(10, 3) MF_CASE_NW(10, 4)
+      default: return pf::fail("pfsgnn mfma", "unsupported Fdim for this edge path");
+    }
+#undef MF_CASE_NW
+  } else if (tmask) {
     MF_LAUNCH3(F, prec, true, km_target_bwd, y, sc, sh, Rs, Wt1, ghS, gz, gxe, part, tmask)
   } else {
     MF_LAUNCH3(F, prec, false, km_target_bwd, y, sc, sh, Rs, Wt1, ghS, gz, gxe, part, tmask)
@@ -1554,19 +1663,61 @@ int target_bwd(const EdgeGeo& geo, int F, const float* y, const float* sc, const
   return 0;
 }
 
+// The (Fdim, precision) pairs whose source_bwd also takes TModel's edge weight
+// gradient (TW) within two waves per SIMD and no scratch: every built pair of
+// Fdim 8 and 10.  Fdim 16 stays on the old form: its source_bwd already spills
+// (60 / 72 bytes of scratch per lane), and with NT more images and
+// accumulators the fp32 form drops to one wave per SIMD (87.5 KB of LDS) and
+// the bf16x3 form spills more (76 bytes).
+bool source_bwd_folds(int F, int prec) {
+  switch (F * 8 + prec) {
+    case 8 * 8 + 0: case 8 * 8 + 1: case 10 * 8 + 0: case 10 * 8 + 1: case 10 * 8 + 2:
+    case 10 * 8 + 3: case 10 * 8 + 4:
+      return true;
+  }
+  return false;
+}
+
 int source_bwd(const EdgeGeo& geo, int F, const float* msg, const float* y, const float* sc,
                const float* sh, const float* QtS, const float* Ws1, const float* Ws2,
                const float* bs2, const float* mean, const float* coef, const float* Rs,
                const float* Wt1, const float* ghS, const float* g_next, const float* mu1,
                const float* inv1, float* g_tot, float* pW2, float* pW1, float* pCol, float* pBN,
-               const uint8_t* tmask, int prec, hipStream_t st) {
+               const uint8_t* tmask, int prec, hipStream_t st, float* pWt) {
+  if (pWt) {   // + TModel's edge weight gradient (TW)
+    if (!(tmask && Rs) || !source_bwd_folds(F, prec))
+      return pf::fail("pfsgnn mfma", "source_bwd: no folded form for this call");
+    if (msg && prec != 0 && prec != 1) return pf::fail("pfsgnn mfma", "message cache: mfma paths only");
+#define MF_CASE_TW(FF, PP, MM)                                                                   \
+  case FF * 8 + PP:                                                                             \
+    hipLaunchKernelGGL((km_source_bwd<FF, PP, true, MM, true>), dim3(edge_grid(geo)), dim3(256), 0, \
+                       st, geo, msg, y, sc, sh, QtS, Ws1, Ws2, bs2, mean, coef, Rs, Wt1, ghS,     \
+                       g_next, mu1, inv1, g_tot, pW2, pW1, pCol, pBN, tmask, pWt);              \
+    break;
+    if (msg) {
+      switch (F * 8 + prec) {
+        MF_CASE_TW(8, 0, true) MF_CASE_TW(8, 1, true) MF_CASE_TW(10, 0, true)
+        MF_CASE_TW(10, 1, true)
+        default: return pf::fail("pfsgnn mfma", "unsupported Fdim for this edge path");
+      }
+    } else {
+      switch (F * 8 + prec) {
+        MF_CASE_TW(8, 0, false) MF_CASE_TW(8, 1, false) MF_CASE_TW(10, 0, false)
+        MF_CASE_TW(10, 1, false) MF_CASE_TW(10, 2, false) MF_CASE_TW(10, 3, false)
+        MF_CASE_TW(10, 4, false)
+        default: return pf::fail("pfsgnn mfma", "unsupported Fdim for this edge path");
+      }
+    }
+#undef MF_CASE_TW
+    return 0;
+  }
   if (msg) {   // the message cache: Fdim 8 / 10 / 16 on the mfma / mfma32 paths
     if (prec != 0 && prec != 1) return pf::fail("pfsgnn mfma", "message cache: mfma paths only");
 #define MF_CASE_MSG(FF, PP, TT)                                                                  \
   case FF * 8 + PP:                                                                             \
     hipLaunchKernelGGL((km_source_bwd<FF, PP, TT, true>), dim3(edge_grid(geo)), dim3(256), 0, st, \
                        geo, msg, y, sc, sh, QtS, Ws1, Ws2, bs2, mean, coef, Rs, Wt1, ghS, g_next, \
-                       mu1, inv1, g_tot, pW2, pW1, pCol, pBN, tmask);                           \
+                       mu1, inv1, g_tot, pW2, pW1, pCol, pBN, tmask, nullptr);                  \
     break;
     if (tmask && Rs) {
       switch (F * 8 + prec) {
@@ -1586,10 +1737,10 @@ int source_bwd(const EdgeGeo& geo, int F, const float* msg, const float* y, cons
   }
   if (tmask && Rs) {
     MF_LAUNCH3(F, prec, true, km_source_bwd, nullptr, y, sc, sh, QtS, Ws1, Ws2, bs2, mean, coef, Rs, Wt1,
-               ghS, g_next, mu1, inv1, g_tot, pW2, pW1, pCol, pBN, tmask)
+               ghS, g_next, mu1, inv1, g_tot, pW2, pW1, pCol, pBN, tmask, nullptr)
   } else {
     MF_LAUNCH3(F, prec, false, km_source_bwd, nullptr, y, sc, sh, QtS, Ws1, Ws2, bs2, mean, coef, Rs, Wt1,
-               ghS, g_next, mu1, inv1, g_tot, pW2, pW1, pCol, pBN, tmask)
+               ghS, g_next, mu1, inv1, g_tot, pW2, pW1, pCol, pBN, tmask, nullptr)
   }
   return 0;
 }

@@ -441,11 +441,13 @@ class Engine:
         return be.moment_coef(st["mom"], gst, d.NC if d.sp is None else d.sp.fib_ptr)
 
     def source_edge_bwd(self, P, Gr, d, pre, st, coef, tpart, g_next, bnstat, g_xt, se=None,
-                        epre=None, tmask=None):
+                        epre=None, tmask=None, dWt1=None):
         """SModel edge backward; with the upstream EdgeModel's state ``se`` (and
         its prefix) the edge BatchNorm's backward coefficients come out of the
         same call -> (g_tot, (alpha, gam0, gam1)); else -> (g_tot, Sg, Sgx).
-        ``tmask``: the TModel forward's mask for ``tpart`` (target_fwd)."""
+        ``tmask``: the TModel forward's mask for ``tpart`` (target_fwd).
+        ``dWt1``: TModel's first-Linear weight gradient when its edge backward
+        ran folded (target_edge_bwd): its [:, F:2F] block is taken here."""
         be, F = self.be, self.F
         Ws1, Ws2 = P[pre + "node_mlp_1.0.weight"], P[pre + "node_mlp_1.2.weight"]
         y, sc, sh = st["xe3"]
@@ -459,7 +461,8 @@ class Engine:
             tpart, g_next, bnstat, Gr[pre + "node_mlp_1.0.weight"], Gr[pre + "node_mlp_1.2.weight"],
             Gr[pre + "node_mlp_1.2.bias"], bn2=bn2, g_xt=g_xt,  # + g_xt += Ws1x^T GzS
             **({"tmask": tmask} if tmask is not None and tpart is not None else {}),
-            **({"msg": st["msg"]} if st.get("msg") is not None else {}))
+            **({"msg": st["msg"]} if st.get("msg") is not None else {}),
+            **({"dWt1": dWt1} if dWt1 is not None else {}))
         g_tot, GzS = out[0], out[1]
         be.wgrad(GzS, st["xt"], Gr[pre + "node_mlp_1.0.weight"], col0=0,
                  db=Gr[pre + "node_mlp_1.0.bias"])
@@ -602,11 +605,20 @@ class Engine:
         return be.lin_t(Wt2, 0, 2 * F, g_agg)
 
     def target_edge_bwd(self, P, Gr, d, pre, st, g_hsum, want_gxe, g_xs, bn_sums=None):
-        """-> gxe; with ``bn_sums`` (_fiber_bn_sums) -> (gxe, BatchNorm sum partials)."""
+        """-> gxe; with ``bn_sums`` (_fiber_bn_sums) -> (gxe, BatchNorm sum partials).
+        With the forward's mask and no gxe on a complete batch the op runs its
+        mask-only form where the backend has the folded pair (tbwd_fold;
+        PFSGNN_TBWD_FOLD=0: today's pair, an A/B knob): st["tfold"] then tells
+        the caller to hand dWt1 to source_edge_bwd, which takes dWt1[:, F:2F]."""
         be, F = self.be, self.F
         Wt1 = P[pre + "node_mlp_1.0.weight"]
         y, sc, sh = st["xe3"]
         kw = {"tmask": st["tmask"]} if st.get("tmask") is not None else {}
+        st["tfold"] = bool(kw and not want_gxe and d.sp is None and hasattr(be, "tbwd_fold")
+                           and os.environ.get("PFSGNN_TBWD_FOLD", "1") != "0"
+                           and be.tbwd_fold(d))
+        if st["tfold"]:
+            kw["fold"] = True
         if bn_sums is not None:
             kw["bn_sums"] = bn_sums
         out = be.target_bwd(d, y, sc, sh, st["Rs"], Wt1, g_hsum,
@@ -793,7 +805,9 @@ class Engine:
                                                    g_xe, bnstat, g_xt_in,
                                                    se=None if ev else se,
                                                    epre=p + "edge_model.",
-                                                   tmask=stt.get("tmask") if live_t else None)
+                                                   tmask=stt.get("tmask") if live_t else None,
+                                                   dWt1=Gr[p + "t_model.node_mlp_1.0.weight"]
+                                                   if live_t and stt.get("tfold") else None)
                 if not self.normed:
                     bnc = None
                 elif ev:

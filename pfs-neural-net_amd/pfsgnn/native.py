@@ -219,6 +219,9 @@ _SIGS = {
     "pfsgnn_tmask_bytes": ([I, I, I, I], SZ),
     "pfsgnn_target_bwd": ([I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, SZ, P], I),
     "pfsgnn_target_bwd_bn": ([I, I, I, I] + [P] * 14 + [FL, P, P, SZ, P], I),
+    "pfsgnn_tbwd_fold": ([I], I),
+    "pfsgnn_target_bwd_fold": ([I, I, I, I] + [P] * 14 + [FL, P, P, SZ, P], I),
+    "pfsgnn_source_bwd_fold": ([I, I, I, I] + [P] * 17 + [LL, FL] + [P] * 16 + [P, SZ, P], I),
     "pfsgnn_source_bwd": ([I, I, I, I] + [P] * 24 + [P, SZ, P], I),
     "pfsgnn_source_bwd_bn": ([I, I, I, I] + [P] * 17 + [LL, FL] + [P] * 12 + [P, SZ, P], I),
     "pfsgnn_msg_bytes": ([I, I, I, I], SZ),
@@ -1198,13 +1201,40 @@ class HipBackend:
               float(bscale), _ptr(A), _ptr(tmask), ws, wsb, _stream())
         return hsum if agg is None else (hsum, A)
 
+    def tbwd_fold(self, d):
+        """Whether the folded pair exists for this batch on the current edge
+        path (pfsgnn_tbwd_fold): target_bwd(fold=True) + source_bwd(dWt1=...)."""
+        return d.sp is None and not self._composed(d) and bool(lib().pfsgnn_tbwd_fold(d.F))
+
     def target_bwd(self, d, y, sc, sh, Rs, Wt1, g_hsum, dWt1, want_gxe=False, g_xs=None,
-                   tmask=None, bn_sums=None):
+                   tmask=None, bn_sums=None, fold=False):
         """-> (GzT, gxe); with ``g_xs``: g_xs += Wt1[:, :F]^T GzT as well;
         ``tmask``: the forward's mask (target_fwd), read instead of recomputed.
         ``bn_sums`` = (Yp, mu, var, eps) of the BatchNorm whose backward reads the
         finished g_xs next (SModel's, gnn.py:154; complete graphs): its sums come
-        out of the same call -> (GzT, gxe, partials for mlp_bwd's bn_part)."""
+        out of the same call -> (GzT, gxe, partials for mlp_bwd's bn_part).
+        ``fold`` (tbwd_fold(d), with ``tmask`` and no gxe): the mask-only form
+        (pfsgnn_target_bwd_fold); dWt1[:, F:2F] is then left to the source_bwd
+        call that follows, which must be given ``dWt1``."""
+        if fold:
+            # (where tbwd_fold(d) is false the entry point runs today's form)
+            assert tmask is not None and not want_gxe and d.sp is None
+            self._chk(g_xs)
+            GzT = self.empty(2 * d.F, d.NS)
+            g_hsum = g_hsum.contiguous()
+            Yp = mu = var = part = None
+            eps = 0.0
+            if bn_sums is not None:
+                assert g_xs is not None
+                Yp, mu, var, eps = bn_sums
+                self._chk(Yp, mu, var)
+                part = self.empty((d.NS + 63) // 64, 32)
+            ws, wsb = self._wsargs(d)
+            _call("pfsgnn_target_bwd_fold", d.G, d.NF, d.NC, d.F, y.data_ptr(), _ptr(sc),
+                  _ptr(sh), Rs.data_ptr(), Wt1.data_ptr(), g_hsum.data_ptr(), GzT.data_ptr(),
+                  dWt1.data_ptr(), None, _ptr(g_xs), tmask.data_ptr(), _ptr(Yp), _ptr(mu),
+                  _ptr(var), float(eps), _ptr(part), ws, wsb, _stream())
+            return (GzT, None) if bn_sums is None else (GzT, None, part)
         if bn_sums is not None:
             assert g_xs is not None and not self._composed(d) and d.sp is None
             Yp, mu, var, eps = bn_sums
@@ -1235,11 +1265,13 @@ class HipBackend:
         return GzT, gxe
 
     def source_bwd(self, d, y, sc, sh, Qt, Ws1, Ws2, bs2, mean, coef, tpart, g_next, bnstat,
-                   dWs1, dWs2, dbs2, bn2=None, g_xt=None, tmask=None, msg=None):
+                   dWs1, dWs2, dbs2, bn2=None, g_xt=None, tmask=None, msg=None, dWt1=None):
         """-> (g_tot, GzS, Sg, Sgx).  With ``bn2`` = (gamma, var1, n, eps, dgamma,
         dbeta) (and ``bnstat``) the edge BatchNorm's backward is finished in the
         same call: -> (g_tot, GzS, None, None, (alpha, gam0, gam1)).  With
-        ``g_xt``: g_xt += Ws1[:, :F]^T GzS as well."""
+        ``g_xt``: g_xt += Ws1[:, :F]^T GzS as well.  ``dWt1``: the second half of
+        the folded pair (target_bwd(fold=True)): dWt1[:, F:2F] += g_zt x^T too."""
+        assert dWt1 is None or (tpart is not None and tmask is not None and d.sp is None)
         if self._composed(d):
             out = self._sp.source_bwd(d, y, sc, sh, Qt, Ws1, Ws2, bs2, mean, coef, tpart, g_next,
                                       bnstat, dWs1, dWs2, dbs2)
@@ -1268,6 +1300,21 @@ class HipBackend:
         head = (d.G, d.NF, d.NC, d.F, y.data_ptr(), _ptr(sc), _ptr(sh), Qt.data_ptr(),
                 Ws1.data_ptr(), Ws2.data_ptr(), bs2.data_ptr(), mean.data_ptr(), coef.data_ptr(),
                 _ptr(Rs), _ptr(Wt1), _ptr(g_hsum), _ptr(g_next), _ptr(mu1), _ptr(inv1))
+        if dWt1 is not None:
+            var1 = gamma = a = g0 = g1 = dg = db = None
+            n, eps = 0, 0.0
+            if bn2 is not None:
+                assert bnstat is not None
+                gamma, var1, n, eps, dg, db = bn2
+                a, g0, g1 = self.empty(d.F), self.empty(d.F), self.empty(d.F)
+            _call("pfsgnn_source_bwd_fold", *head, _ptr(var1), _ptr(gamma), int(n), float(eps),
+                  g_tot.data_ptr(), GzS.data_ptr(), dWs1.data_ptr(), dWs2.data_ptr(),
+                  dbs2.data_ptr(), _ptr(Sg), _ptr(Sgx), _ptr(a), _ptr(g0), _ptr(g1), _ptr(dg),
+                  _ptr(db), _ptr(g_xt), tmask.data_ptr(), _ptr(msg), dWt1.data_ptr(), ws, wsb,
+                  _stream())
+            if bn2 is not None:
+                return g_tot, GzS, None, None, (a, g0, g1)
+            return g_tot, GzS, Sg, Sgx
         if bn2 is not None:
             assert bnstat is not None
             gamma, var1, n, eps, dg, db = bn2
