@@ -913,6 +913,66 @@ int pfsgnn_loss_bwd_bn(int G, int NF, int NC, int F, const float* y, const float
                        const float* bn_inv1, float* bn_part, void* ws, size_t ws_bytes,
                        void* stream);
 
+/* The objective on a SLICED GENERAL batch (pfsgnn_sliced_t; pfsgnn_sl_loss.hip):
+ * the three ops above with the layout and pos_user [EP] (pfsgnn_sliced_fill:
+ * the caller's edge at each position, -1 at padding) in front of the same
+ * arguments.  Replaces train.py:36-71 and decoder_e / edge_prediction
+ * (gnn.py:307-312) for a batch whose fibers reach only some classes.
+ *
+ * train.py indexes edges by position (train.py:40, :67), which only means
+ * something on the complete fiber-major graph; here every edge e = (src_e,
+ * tgt_e) is indexed by edge_index:
+ *   time_e = softplus(decoder_e(x_e)) * scale   (scale = TOTAL_TIME / NC, NC the
+ *            classes per graph);  T_e = ci[0][tgt_e];
+ *   galaxies_e = max(0, softfloor(time_e / T_e));  tt_e = galaxies_e * T_e;
+ *   n'_c = sum of galaxies_e over tgt_e = c;  fiber_time_f = sum of tt_e over
+ *   src_e = f -- a fiber without edges has fiber_time 0 and still pays its
+ *   leaky under-time penalty (scatter with dim_size = NFIBERS);
+ *   completeness_c = n'_c / (N_c / nfields), utils_g its minimum over the
+ *   graph's classes (a class without edges: 0; ties split the gradient evenly,
+ *   a NaN propagates);
+ *   variance_g = sum over c of the unbiased variance of tt_e over the deg(c)
+ *   edges with tgt_e = c.  A class with deg(c) < 2 contributes 0 and gets no
+ *   variance gradient -- the one divergence from the reference, whose
+ *   torch.var would give NaN there;
+ *   class and fiber penalties and the sum over graphs as pfsgnn_loss_finalize.
+ * softfloor's uniform of edge e is the counter-based hash of (seed, e) with e
+ * the CALLER's edge position (pos_user) -- the dense kernels' counter,
+ * independent of the sliced layout.  On a complete fiber-major batch the
+ * values equal the dense ops'.
+ *
+ * Shapes: y, gxe [F][sl->EP] in slot order (gxe: every position written, 0 at
+ * padding); tt (optional) [sl->E] in the caller's edge order; n_prime, tmean,
+ * Gn, Gv [G*NC]; fiber_time, Gf [G*NF]; tvar [2][G*NC]: row 0 the class
+ * variances, row 1 the class edge counts deg(c) of the reduction (read by
+ * pfsgnn_sl_loss_finalize for the variance gradient).  Workspace:
+ * pfsgnn_workspace_bytes.  No host synchronisation, no allocation, no atomics:
+ * capturable and bitwise reproducible.  Refused with an error text before any
+ * launch: Fdim outside 8 / 10 / 16, NC above pfsgnn_sliced_max_nc (including
+ * edge paths without sliced kernels). */
+int pfsgnn_sl_loss_fwd(const pfsgnn_sliced_t* sl, const int* pos_user, int G, int NF, int NC,
+                       int F, const float* y, const float* sc, const float* sh, const float* Wd1,
+                       const float* bd1, const float* Wd2, const float* bd2, const float* ci,
+                       float scale, float sharpness, float noiselevel, unsigned long long seed,
+                       const unsigned long long* seed_dev, float* n_prime, float* fiber_time,
+                       float* tmean, float* tvar, float* tt, void* ws, size_t ws_bytes,
+                       void* stream);
+int pfsgnn_sl_loss_finalize(const pfsgnn_sliced_t* sl, const int* pos_user, int G, int NF, int NC,
+                            const float* n_prime, const float* fiber_time, const float* tvar,
+                            const float* ci, float pclass, float pfiber, float total_time,
+                            float nfields, float wutils, float wvar, float* loss, float* utils,
+                            float* variance, float* Gn, float* Gf, float* Gv, void* stream);
+/* (the final EdgeModel BatchNorm's backward sums are not fused here: a sliced
+ * batch takes pfsgnn_rows_bn_sums over gxe and y) */
+int pfsgnn_sl_loss_bwd(const pfsgnn_sliced_t* sl, const int* pos_user, int G, int NF, int NC,
+                       int F, const float* y, const float* sc, const float* sh, const float* Wd1,
+                       const float* bd1, const float* Wd2, const float* bd2, const float* ci,
+                       float scale, float sharpness, float noiselevel, unsigned long long seed,
+                       const unsigned long long* seed_dev, const float* Gn, const float* Gf,
+                       const float* Gv, const float* tmean, const float* gscale, float* dWd1,
+                       float* dbd1, float* dWd2, float* dbd2, float* gxe, void* ws,
+                       size_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------- layout
  * The reference takes an arbitrary edge_index [2][E] (int64, gnn.py:7).  A
  * complete bipartite batch in any edge order maps onto the canonical

@@ -1,6 +1,7 @@
 // pfsgnn_loss.hip -- the training objective (train.py:21-80) fused over edges,
 // and the edge-layout helpers (canonical order <-> the caller's edge_index).
 #include "pfsgnn_common.h"
+#include "pfsgnn_loss_core.h"   // the per-edge arithmetic, class reduce and finalize
 #include "../../include/pfsgnn.h"
 
 #include <algorithm>
@@ -44,92 +45,6 @@
   _Pragma("unroll") for (int k = 0; k < F; ++k)                             \
     x[k] = sc ? fmaf(yq[k], sc[k], sh[k]) : yq[k];                          \
   yload(c + 4);
-
-__device__ __forceinline__ void wave_lds_sync() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_wave_barrier();
-}
-
-struct SoftFloor {
-  float r, corr, two_pi, inv_pi;  // r = exp(-1/sharpness) (0 if sharpness == 0)
-};
-
-static SoftFloor make_softfloor(float sharpness) {
-  SoftFloor s;
-  const float pi = (float)M_PI;                           // x.new_tensor(np.pi)
-  s.r = sharpness == 0.f ? 0.f : expf(-1.0f / sharpness); // train.py:26
-  s.corr = atanf(s.r / (1.0f - s.r));
-  s.two_pi = 2.0f * pi;
-  s.inv_pi = 1.0f / pi;
-  return s;
-}
-
-// decoder_e + softplus*scale + softfloor + clamp (train.py:42-49, gnn.py:307-312).
-// LOSS_FAST: sin / cos of 2 pi x as one sincospi of 2x (the reduction is exact
-// in revolutions, no large-argument path) and one reciprocal of T_i per edge
-// for the two divisions by it
-#ifndef LOSS_FAST
-#define LOSS_FAST 1
-#endif
-template <int F>
-struct EdgeLoss {
-  float zd[F], ad[F], pred, time, Ti, xx, th, graw, gal, tt, cth, invTi;
-  __device__ __forceinline__ void run(const float (&x)[F], const float* __restrict__ Wd1,
-                                      const float* __restrict__ bd1, const float* __restrict__ Wd2,
-                                      const float* __restrict__ bd2, float scale, float Ti_,
-                                      float noise, const SoftFloor& sf) {
-    pred = bd2[0];
-#pragma unroll
-    for (int j = 0; j < F; ++j) {
-      float s = bd1[j];
-#pragma unroll
-      for (int k = 0; k < F; ++k) s = fmaf(Wd1[j * F + k], x[k], s);
-      zd[j] = s;
-      ad[j] = lrelu(s);
-      pred = fmaf(Wd2[j], ad[j], pred);
-    }
-    const float sp = pred > 20.f ? pred : log1pf(expf(pred));  // F.softplus (threshold 20)
-    time = sp * scale;
-    Ti = Ti_;
-#if LOSS_FAST
-    invTi = 1.0f / Ti;
-    xx = fmaf(time, invTi, noise);
-    float sth;
-    sincospif(2.0f * xx, &sth, &cth);
-    graw = xx + sf.inv_pi * (atanf(sf.r * sth / (1.0f - sf.r * cth)) - sf.corr);
-#else
-    xx = time / Ti + noise;
-    th = sf.two_pi * xx;
-    cth = cosf(th);
-    graw = xx + sf.inv_pi * (atanf(sf.r * sinf(th) / (1.0f - sf.r * cth)) - sf.corr);
-#endif
-    gal = graw < 0.f ? 0.f : graw;  // torch.maximum(0, g) (NaN propagates)
-    tt = gal * Ti;
-  }
-};
-
-// decoder_e's weights staged in LDS (read as broadcasts inside the edge loop):
-// held in SGPRs they overflowed the scalar file (119 / 139 SGPR spills, each
-// use a v_readlane in the loop)
-template <int F>
-struct DecW {
-  static constexpr int N = F * F + 2 * F + 1;
-  float w[N];   // Wd1 [F][F] | bd1 [F] | Wd2 [F] | bd2
-  __device__ __forceinline__ void load(const float* __restrict__ Wd1, const float* __restrict__ bd1,
-                                       const float* __restrict__ Wd2, const float* __restrict__ bd2) {
-    for (int i = threadIdx.x; i < N; i += blockDim.x)
-      w[i] = i < F * F ? Wd1[i] : i < F * F + F ? bd1[i - F * F]
-                                : i < F * F + 2 * F ? Wd2[i - F * F - F] : bd2[0];
-  }
-};
-// the weights' base as an opaque value per loop iteration: the compiler would
-// otherwise hoist all F*F + 2F + 1 loop-invariant reads into VGPRs (occupancy 7 -> 3)
-template <int F>
-__device__ __forceinline__ const float* dec_base(const DecW<F>& d) {
-  int lo = 0;
-  asm volatile("" : "+v"(lo));
-  return d.w + lo;
-}
 
 template <int F>
 __global__ __launch_bounds__(256) void k_loss_fwd(EdgeGeo geo, const float* __restrict__ y,
@@ -181,116 +96,6 @@ __global__ __launch_bounds__(256) void k_loss_fwd(EdgeGeo geo, const float* __re
   if (t < 64 && t < nvalid)
     fiber_time[(size_t)ks * NS + nbase + t] =
         ((scratch[t] + scratch[64 + t]) + scratch[128 + t]) + scratch[192 + t];
-}
-
-__device__ __forceinline__ double wave_dsum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
-// one wave per class: lane l takes the fiber groups l, l + 64, ... and the
-// moments merge in closed form (mean = sum c_b m_b / sum c_b, M2 = sum (q_b +
-// c_b (m_b - mean)^2), in double; fixed lane and butterfly order): the loads
-// are independent, where a per-thread Chan chain ran NFG dependent divisions
-__global__ __launch_bounds__(256) void k_loss_class_reduce(const float* __restrict__ part, int G,
-                                                           int NFG, int NC, int NF,
-                                                           float* __restrict__ n_prime,
-                                                           float* __restrict__ tmean,
-                                                           float* __restrict__ tvar) {
-  const int idx = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;  // over G*NC
-  if (idx >= G * NC) return;
-  const int g = idx / NC, c = idx - g * NC;
-  const float* q0 = part + ((size_t)g * NFG * NC + c) * 4;
-  const size_t stride = (size_t)NC * 4;
-  double P = 0, C = 0, S = 0;
-  for (int b = lane; b < NFG; b += 64) {
-    const float* q = q0 + (size_t)b * stride;
-    P += q[0];
-    C += q[1];
-    S += (double)q[1] * (double)q[2];
-  }
-  P = wave_dsum(P);
-  C = wave_dsum(C);
-  S = wave_dsum(S);
-  const double M = C > 0 ? S / C : 0.0;
-  double Q = 0;
-  for (int b = lane; b < NFG; b += 64) {
-    const float* q = q0 + (size_t)b * stride;
-    const double d = (double)q[2] - M;
-    Q += (double)q[3] + (double)q[1] * d * d;
-  }
-  Q = wave_dsum(Q);
-  if (lane == 0) {
-    n_prime[idx] = (float)P;
-    tmean[idx] = (float)M;
-    tvar[idx] = NF > 1 ? (float)(Q / (double)(NF - 1)) : NAN;  // torch.var, correction=1
-  }
-}
-
-// torch.min propagates NaN (train.py:53: a class with N_i = 0 gives 0/0);
-// fminf would drop it
-__device__ __forceinline__ float nan_min(float a, float b) {
-  return (a != a) ? a : ((b != b) ? b : (b < a ? b : a));
-}
-
-// one block per graph: train.py:53-71 and the per-node gradient coefficients
-__global__ __launch_bounds__(256) void k_loss_finalize(
-    int NF, int NC, int NT, const float* __restrict__ n_prime, const float* __restrict__ fiber_time,
-    const float* __restrict__ tvar, const float* __restrict__ ci, float pclass, float pfiber,
-    float total_time, float nfields, float wutils, float wvar, float* __restrict__ loss,
-    float* __restrict__ utils, float* __restrict__ variance, float* __restrict__ Gn,
-    float* __restrict__ Gf, float* __restrict__ Gv) {
-  const int g = blockIdx.x, t = threadIdx.x;
-  __shared__ float scratch[4 * 4];
-  __shared__ float smin[256];
-  // completeness min
-  float mn = INFINITY;
-  for (int c = t; c < NC; c += 256) {
-    const long long cn = (long long)g * NC + c;
-    const float Ni = ci[NT + cn] / nfields;
-    const float comp = n_prime[cn] / Ni;
-    mn = nan_min(mn, comp);
-  }
-  smin[t] = mn;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (t < s) smin[t] = nan_min(smin[t], smin[t + s]);
-    __syncthreads();
-  }
-  const float umin = smin[0];
-  float v[4] = {0.f, 0.f, 0.f, 0.f};  // ties, class penalty, fiber penalty, variance
-  for (int c = t; c < NC; c += 256) {
-    const long long cn = (long long)g * NC + c;
-    const float Ni = ci[NT + cn] / nfields;
-    const float comp = n_prime[cn] / Ni;
-    v[0] += comp == umin ? 1.f : 0.f;
-    const float over = fmaxf(n_prime[cn] - Ni, 0.f);
-    v[1] += over * over;
-    v[3] += tvar[cn];
-  }
-  for (int f = t; f < NF; f += 256) {
-    const long long n = (long long)g * NF + f;
-    const float ot = fiber_time[n] - total_time;
-    const float lk = lrelu(ot);
-    v[2] += lk * lk;
-    Gf[n] = pfiber * 2.f * lk * dlrelu(ot);
-  }
-  block_sum<4>(v, scratch);
-  const float ties = v[0];
-  for (int c = t; c < NC; c += 256) {
-    const long long cn = (long long)g * NC + c;
-    const float Ni = ci[NT + cn] / nfields;
-    const float comp = n_prime[cn] / Ni;
-    const float over = fmaxf(n_prime[cn] - Ni, 0.f);
-    Gn[cn] = (comp == umin ? -wutils / ties : 0.f) / Ni + 2.f * pclass * over;
-    Gv[cn] = -wvar * 2.f / (float)(NF - 1);
-  }
-  if (t == 0) {
-    utils[g] = umin;
-    variance[g] = v[3];
-    loss[g] = -wutils * umin + pfiber * v[2] + pclass * v[1] - wvar * v[3];
-  }
 }
 
 template <int F, bool BN>
@@ -536,31 +341,14 @@ __global__ void k_fiber_partial_sum(const float* __restrict__ part, int KS, long
 
 // ------------------------------------------------------------ host side
 namespace {
-struct Ws {
-  char* p;
-  size_t left;
-  float* take(size_t nfloats) {
-    const size_t b = align256(nfloats * sizeof(float));
-    if (b > left) return nullptr;
-    float* r = reinterpret_cast<float*>(p);
-    p += b;
-    left -= b;
-    return r;
-  }
-};
+using Ws = LossWs;
+#define DISPATCH_F LOSS_DISPATCH_F
 int check_dims(const char* where, int G, int NF, int NC, int F) {
   if (G <= 0 || NF <= 1 || NC <= 0) return pf::fail(where, "need G > 0, NF > 1, NC > 0");
   if (NC > 256) return pf::fail(where, "NC > 256 is not supported by the dense edge kernels");
   if (F != 8 && F != 10 && F != 16) return pf::fail(where, "unsupported Fdim (8, 10, 16)");
   return 0;
 }
-#define DISPATCH_F(F, ...)                                   \
-  switch (F) {                                               \
-    case 8: { constexpr int FF = 8; __VA_ARGS__; } break;    \
-    case 10: { constexpr int FF = 10; __VA_ARGS__; } break;  \
-    case 16: { constexpr int FF = 16; __VA_ARGS__; } break;  \
-    default: return pf::fail("dispatch", "unsupported F");   \
-  }
 // the loss kernels' grid: class splits to about PFSGNN_LOSS_BLOCKS blocks
 // (A/B knob; default PF_TARGET_BLOCKS)
 EdgeGeo loss_geo(int G, int NF, int NC) {
@@ -598,7 +386,7 @@ extern "C" int pfsgnn_loss_fwd(int G, int NF, int NC, int F, const float* y, con
   if (geo.KS > 1)
     hipLaunchKernelGGL(k_fiber_partial_sum, dim3((unsigned)((geo.NS + 255) / 256)), dim3(256), 0,
                        st, ftp, geo.KS, geo.NS, fiber_time);
-  hipLaunchKernelGGL(k_loss_class_reduce, dim3((G * NC + 3) / 4), dim3(256), 0, st, part, G,
+  hipLaunchKernelGGL(k_loss_class_reduce<false>, dim3((G * NC + 3) / 4), dim3(256), 0, st, part, G,
                      geo.NFG, NC, NF, n_prime, tmean, tvar);
   return pf::check_launch("pfsgnn_loss_fwd");
 }
@@ -612,7 +400,7 @@ extern "C" int pfsgnn_loss_finalize(int G, int NF, int NC, const float* n_prime,
   PF_REQUIRE(G > 0 && NF > 1 && NC > 0, "pfsgnn_loss_finalize", "bad dims");
   PF_REQUIRE(n_prime && fiber_time && tvar && ci && loss && utils && variance && Gn && Gf && Gv,
              "pfsgnn_loss_finalize", "null");
-  hipLaunchKernelGGL(k_loss_finalize, dim3(G), dim3(256), 0, as_stream(stream), NF, NC, G * NC,
+  hipLaunchKernelGGL(k_loss_finalize<false>, dim3(G), dim3(256), 0, as_stream(stream), NF, NC, G * NC,
                      n_prime, fiber_time, tvar, ci, pclass, pfiber, total_time, nfields, wutils,
                      wvar, loss, utils, variance, Gn, Gf, Gv);
   return pf::check_launch("pfsgnn_loss_finalize");

@@ -843,7 +843,10 @@ class Engine:
     def loss_forward(self, P, d, xe3, ci, sharpness, seed, pclass=0.1, pfiber=0.1, total_time=42.0,
                      nfields=10, wutils=2000.0, wvar=1.0, noiselevel=0.3, want_time=False):
         """train.py:29-80 on the final edge state ``xe3``.  ``ci`` = class_info
-        channel-major [>=2, NT] (row 0 = T_i hours per visit, row 1 = N_i)."""
+        channel-major [>=2, NT] (row 0 = T_i hours per visit, row 1 = N_i).
+        On a sliced general batch (``d.sp.sl``) the backend runs the
+        edge_index-indexed form (include/pfsgnn.h, pfsgnn_sl_loss_fwd): xe3 in
+        slot order, ``time`` in the caller's edge order."""
         be = self.be
         y, sc, sh = xe3
         scale = total_time / d.NC                     # TOTAL_TIME/NCLASSES, train.py:42
@@ -861,9 +864,13 @@ class Engine:
     def loss_bnstat(self, ectx):
         """(mu1, inv1) of the final block's edge BatchNorm when the loss
         backward can make its backward sums (training statistics, complete
-        batch, a backend with loss_bwd(bn=...)); else None."""
+        batch, a backend with loss_bwd(bn=...)); else None.  A general batch
+        (``d.sp`` set) gets None: the sliced loss backward does not fuse the
+        sums, the edge_bn_grad_sums pass makes them."""
         blocks = ectx.get("blocks") if ectx is not None else None
+        d = ectx.get("d") if ectx is not None else None
         if (not blocks or not self.normed or not ectx.get("training", True)
+                or (d is not None and d.sp is not None)
                 or not getattr(self.be, "loss_bn_part", False)
                 or os.environ.get("PFSGNN_LOSS_BN_SUMS", "1") == "0"):
             return None

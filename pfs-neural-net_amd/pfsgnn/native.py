@@ -261,6 +261,9 @@ _SIGS = {
 for _op in ("edge_mlp_fwd", "edge_mlp_fwd_bn", "source_fwd", "target_fwd", "target_bwd",
             "source_bwd", "source_bwd_bn", "edge_mlp_bwd"):
     _SIGS["pfsgnn_sl_" + _op] = ([SLP] + _SIGS["pfsgnn_" + _op][0], I)
+# the objective on a sliced general batch: the layout and pos_user, then the dense op's arguments
+for _op in ("loss_fwd", "loss_finalize", "loss_bwd"):
+    _SIGS["pfsgnn_sl_" + _op] = ([SLP, P] + _SIGS["pfsgnn_" + _op][0], I)
 
 
 def lib():
@@ -1392,18 +1395,46 @@ class HipBackend:
             return 0, seed.data_ptr()
         return int(seed) & ((1 << 64) - 1), None
 
+    @staticmethod
+    def _loss_layout(d):
+        """The sliced layout of a general batch (None: a complete batch).  The
+        objective has no composed form: it runs on the fused sliced kernels only."""
+        if d.sp is None:
+            return None
+        if d.sp.sl is None:
+            raise NotImplementedError(
+                "the training objective on a general (non-complete) batch runs on the fused "
+                "sliced kernels only; this batch is on the composed path (PFSGNN_SLICED=0, more "
+                "classes per graph than pfsgnn_sliced_max_nc, or a bf16 edge-state path)")
+        return d.sp.sl
+
+    @staticmethod
+    def _lcall(op, sl, *args):
+        """pfsgnn_<op>, or pfsgnn_sl_<op>(layout, pos_user, same arguments) on a sliced batch."""
+        if sl is None:
+            _call("pfsgnn_" + op, *args)
+        else:
+            _call("pfsgnn_sl_" + op, sl.ref, sl.pos_user.data_ptr(), *args)
+
     def loss_fwd(self, d, y, sc, sh, Wd1, bd1, Wd2, bd2, ci, scale, sharpness, noiselevel, seed,
                  want_time=False):
+        """On a sliced general batch (``d.sp.sl``): y is [F, EP] in slot order,
+        tt [E] in the caller's edge order, and tvar is [2, NT] -- the class
+        variances and, for loss_finalize, the class edge counts
+        (pfsgnn_sl_loss_fwd)."""
+        sl = self._loss_layout(d)
         n_prime, fiber_time = self.empty(d.NT), self.empty(d.NS)
-        tmean, tvar = self.empty(d.NT), self.empty(d.NT)
+        tmean = self.empty(d.NT)
+        tvar = self.empty(d.NT) if sl is None else self.empty(2, d.NT)
         tt = self.empty(d.E) if want_time else None
         ci = ci.contiguous()
+        assert sl is None or tuple(y.shape) == (d.F, sl.EP), (tuple(y.shape), d.F, sl.EP)
         ws, wsb = self._wsargs(d)
-        _call("pfsgnn_loss_fwd", d.G, d.NF, d.NC, d.F, y.data_ptr(), _ptr(sc), _ptr(sh),
-              Wd1.data_ptr(), bd1.data_ptr(), Wd2.data_ptr(), bd2.data_ptr(), ci.data_ptr(),
-              float(scale), float(sharpness), float(noiselevel), *self._seed_args(seed),
-              n_prime.data_ptr(), fiber_time.data_ptr(), tmean.data_ptr(), tvar.data_ptr(),
-              _ptr(tt), ws, wsb, _stream())
+        self._lcall("loss_fwd", sl, d.G, d.NF, d.NC, d.F, y.data_ptr(), _ptr(sc), _ptr(sh),
+                    Wd1.data_ptr(), bd1.data_ptr(), Wd2.data_ptr(), bd2.data_ptr(), ci.data_ptr(),
+                    float(scale), float(sharpness), float(noiselevel), *self._seed_args(seed),
+                    n_prime.data_ptr(), fiber_time.data_ptr(), tmean.data_ptr(), tvar.data_ptr(),
+                    _ptr(tt), ws, wsb, _stream())
         return n_prime, fiber_time, tmean, tvar, tt
 
     def loss_finalize(self, d, n_prime, fiber_time, tvar, ci, pclass, pfiber, total_time, nfields,
@@ -1411,17 +1442,25 @@ class HipBackend:
         loss, utils, variance = self.empty(d.G), self.empty(d.G), self.empty(d.G)
         Gn, Gf, Gv = self.empty(d.NT), self.empty(d.NS), self.empty(d.NT)
         ci = ci.contiguous()
-        _call("pfsgnn_loss_finalize", d.G, d.NF, d.NC, n_prime.data_ptr(), fiber_time.data_ptr(),
-              tvar.data_ptr(), ci.data_ptr(), float(pclass), float(pfiber), float(total_time),
-              float(nfields), float(wutils), float(wvar), loss.data_ptr(), utils.data_ptr(),
-              variance.data_ptr(), Gn.data_ptr(), Gf.data_ptr(), Gv.data_ptr(), _stream())
+        sl = self._loss_layout(d)
+        assert tvar.is_contiguous() and tvar.numel() == (d.NT if sl is None else 2 * d.NT)
+        self._lcall("loss_finalize", sl, d.G, d.NF, d.NC, n_prime.data_ptr(),
+                    fiber_time.data_ptr(), tvar.data_ptr(), ci.data_ptr(), float(pclass),
+                    float(pfiber), float(total_time), float(nfields), float(wutils), float(wvar),
+                    loss.data_ptr(), utils.data_ptr(), variance.data_ptr(), Gn.data_ptr(),
+                    Gf.data_ptr(), Gv.data_ptr(), _stream())
         return loss, utils, variance, Gn, Gf, Gv
 
     def loss_bwd(self, d, y, sc, sh, Wd1, bd1, Wd2, bd2, ci, scale, sharpness, noiselevel, seed,
                  Gn, Gf, Gv, tmean, gscale, dWd1, dbd1, dWd2, dbd2, bn=None):
         """-> gxe; with ``bn`` = (mu1, inv1) of the final edge BatchNorm ->
-        (gxe, its backward sums' per-block partials) (pfsgnn_loss_bwd_bn)."""
-        gxe = self.empty(d.F, d.E)
+        (gxe, its backward sums' per-block partials) (pfsgnn_loss_bwd_bn).
+        On a sliced general batch gxe is [F, EP] in slot order (0 at padding)
+        and ``bn`` is not available (Engine.loss_bnstat gives None)."""
+        sl = self._loss_layout(d)
+        if sl is not None and bn is not None:
+            raise NotImplementedError("loss_bwd(bn=...) is not fused on a sliced general batch")
+        gxe = self.empty(d.F, d.EP)
         gs = None
         if isinstance(gscale, torch.Tensor):
             gs = gscale.reshape(1).to(torch.float32).contiguous()
@@ -1441,12 +1480,12 @@ class HipBackend:
                   gxe.data_ptr(), mu1.data_ptr(), inv1.data_ptr(), part.data_ptr(), ws, wsb,
                   _stream())
             return gxe, part
-        _call("pfsgnn_loss_bwd", d.G, d.NF, d.NC, d.F, y.data_ptr(), _ptr(sc), _ptr(sh),
-              Wd1.data_ptr(), bd1.data_ptr(), Wd2.data_ptr(), bd2.data_ptr(), ci.data_ptr(),
-              float(scale), float(sharpness), float(noiselevel), *self._seed_args(seed),
-              Gn.data_ptr(), Gf.data_ptr(), Gv.data_ptr(), tmean.data_ptr(), _ptr(gs),
-              dWd1.data_ptr(), dbd1.data_ptr(), dWd2.data_ptr(), dbd2.data_ptr(), gxe.data_ptr(),
-              ws, wsb, _stream())
+        self._lcall("loss_bwd", sl, d.G, d.NF, d.NC, d.F, y.data_ptr(), _ptr(sc), _ptr(sh),
+                    Wd1.data_ptr(), bd1.data_ptr(), Wd2.data_ptr(), bd2.data_ptr(), ci.data_ptr(),
+                    float(scale), float(sharpness), float(noiselevel), *self._seed_args(seed),
+                    Gn.data_ptr(), Gf.data_ptr(), Gv.data_ptr(), tmean.data_ptr(), _ptr(gs),
+                    dWd1.data_ptr(), dbd1.data_ptr(), dWd2.data_ptr(), dbd2.data_ptr(),
+                    gxe.data_ptr(), ws, wsb, _stream())
         return gxe
 
     # ------------------------------------------------------------ graph building

@@ -102,8 +102,27 @@ def loss_function(graph, class_info, pclass=0.1, pfiber=1.0, sharpness=0.5, fina
     is [NC, 2] (T_i, N_i) per class -- [G*NC, 2] for a batch of G graphs, whose
     loss is the sum of the per-graph losses.  The reference reads the model
     from a global ``gnn`` (train.py:42); here it comes with the graph (or
-    ``gnn=``).  Edge order must be the fiber-major layout train.py builds
-    (train.py:94), on which train.py:40 and :67 rely.  ``seed`` (softfloor's
+    ``gnn=``).  On complete graphs the edge order must be the fiber-major layout
+    train.py builds (train.py:94), on which train.py:40 and :67 rely.
+
+    General (non-complete) batches -- ragged degrees, missing or repeated
+    (fiber, class) pairs, empty fibers or classes -- are accepted when they run
+    on the fused sliced kernels (``Layout.SLOTS``: at most
+    ``pfsgnn_sliced_max_nc`` classes per graph, an fp32 edge-state path,
+    PFSGNN_SLICED not 0).  The objective is then indexed by ``edge_index``
+    instead of by position: ``T_e = class_info[tgt_e, 0]``, ``n'_c`` sums
+    galaxies over ``tgt_e = c``, ``fiber_time_f`` sums time over ``src_e = f``
+    (0 for a fiber without edges, which still pays the under-time penalty), a
+    class without edges has completeness 0, and ``variance`` is the sum over
+    classes of the unbiased variance of time over the class's own ``deg(c)``
+    edges.  One divergence from the reference: a class with ``deg(c) < 2``
+    contributes 0 to the variance (and gets no gradient from it) where
+    ``torch.var`` would give NaN.  softfloor's uniform of edge ``e`` is the
+    counter hash of ``(seed, e)`` with ``e`` the caller's edge position, as on
+    complete graphs.  ``class_info`` stays [G*NC, >=2]; with ``finaloutput``
+    ``comp`` is per class, ``fibers`` per fiber and ``time`` [E] in the
+    caller's edge order.  On a complete fiber-major batch this form equals the
+    reference's.  ``seed`` (softfloor's
     noise): None draws one from torch's CPU generator; an int; or a device
     int64 tensor read in-kernel (a captured step then draws fresh noise per
     replay when the tensor is advanced on the device).  ``noiselevel`` is
@@ -121,7 +140,16 @@ def loss_function(graph, class_info, pclass=0.1, pfiber=1.0, sharpness=0.5, fina
         token = xe3[0].new_empty(())
     if gnn is not None and gnn is not model:
         raise ValueError("graph was produced by a different GNN than `gnn`")
-    if not lay.fiber_major:
+    if lay.sp is not None:
+        # a general batch: the edge_index-indexed objective of the fused sliced kernels
+        if lay.sp.sl is None:
+            raise NotImplementedError(
+                "loss_function on a general (non-complete) batch runs on the fused sliced "
+                "kernels (pfsgnn_sl_loss_*) only, and this batch is on the composed path: "
+                "unset PFSGNN_SLICED=0, keep the classes per graph within "
+                "pfsgnn_sliced_max_nc (at most 128) and use an fp32 edge-state path "
+                "(not \"bf16\" / \"bf16y\"); or materialise out.x_e and write the loss in torch")
+    elif not lay.fiber_major:
         raise NotImplementedError("train.py's objective indexes edges by position "
                                   "(train.py:40, :67): it needs the fiber-major edge order")
     ci = _class_info_cm(class_info, d)

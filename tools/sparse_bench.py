@@ -2,14 +2,17 @@
 complete-graph path, on the bench geometry (GPU box).
 
 The objective is a fixed random linear functional of the GNN outputs (x_s,
-x_t, x_e, u) -- train.py's loss needs complete fiber-major graphs -- and the
+x_t, x_e, u) (--objective linear, the default) or the library's training
+objective, pfsgnn.train.loss_function with a device seed advanced every step
+(--objective train: the sliced loss kernels on general batches, the dense ones
+on the complete batch; not available with PFSGNN_SLICED=0).  The
 step is zero_grad + GNN forward + objective + backward + FusedAdam, captured
 as a HIP graph and replayed (as bench.py times the headline; SPARSE_GRAPH=0:
 eager launches), synchronised around the timed steps; the median of
 SPARSE_RUNS (default 5) timed runs is reported, with the spread.  The edge
 kernels' eager per-step times (pfsgnn timing) follow each line.
 
-    python tools/sparse_bench.py [G] [NF] [NC] [B] [steps]
+    python tools/sparse_bench.py [--objective {linear,train}] [G] [NF] [NC] [B] [steps]
 """
 import os
 import sys
@@ -23,11 +26,20 @@ import torch  # noqa: E402
 import pfsgnn  # noqa: E402
 from pfsgnn import config  # noqa: E402
 
-G = int(sys.argv[1]) if len(sys.argv) > 1 else 16
-NF = int(sys.argv[2]) if len(sys.argv) > 2 else 2394
-NC = int(sys.argv[3]) if len(sys.argv) > 3 else 128
-B = int(sys.argv[4]) if len(sys.argv) > 4 else 8
-STEPS = int(sys.argv[5]) if len(sys.argv) > 5 else 20
+ARGV = sys.argv[1:]
+OBJECTIVE = "linear"
+for i, a in enumerate(ARGV):
+    if a == "--objective" or a.startswith("--objective="):
+        OBJECTIVE = a.split("=", 1)[1] if "=" in a else ARGV[i + 1]
+        del ARGV[i:i + (1 if "=" in a else 2)]
+        break
+if OBJECTIVE not in ("linear", "train"):
+    sys.exit(f"--objective must be linear or train, got {OBJECTIVE!r}")
+G = int(ARGV[0]) if len(ARGV) > 0 else 16
+NF = int(ARGV[1]) if len(ARGV) > 1 else 2394
+NC = int(ARGV[2]) if len(ARGV) > 2 else 128
+B = int(ARGV[3]) if len(ARGV) > 3 else 8
+STEPS = int(ARGV[4]) if len(ARGV) > 4 else 20
 F = 10
 config.device = torch.device("cuda")
 gen = torch.Generator().manual_seed(0)
@@ -58,11 +70,19 @@ def run(density, label):
     opt = pfsgnn.FusedAdam(gnn.parameters(), lr=1e-4, capturable=use_graph)
     w = [torch.randn(n, F, device="cuda") * 1e-3 for n in (G * NF, G * NC, E, G)]
 
+    ci = xt.cuda()
+    seed = torch.full((), 1, dtype=torch.int64, device="cuda")
+
     def step():
         gnn.zero_grad()
         out = gnn(data)
-        loss = ((out.x_s * w[0]).sum() + (out.x_t * w[1]).sum() + (out.x_e * w[2]).sum()
-                + (out.x_u * w[3]).sum())
+        if OBJECTIVE == "train":
+            seed.add_(1)
+            loss, _ = pfsgnn.train.loss_function(out, ci, pclass=0.1, pfiber=0.1, sharpness=8.0,
+                                                 seed=seed)
+        else:
+            loss = ((out.x_s * w[0]).sum() + (out.x_t * w[1]).sum() + (out.x_e * w[2]).sum()
+                    + (out.x_u * w[3]).sum())
         loss.backward()
         opt.step()
 
@@ -108,7 +128,8 @@ def run(density, label):
         if e[0]() is data.edge_index and e[3].sp is not None and e[3].sp.sl is not None:
             pad = f"  EP/E {e[3].sp.sl.EP / E:.3f}"
     print(f"{label:34s} E={E:9d}  {ms:8.2f} ms/step  {E / ms / 1e3:8.1f} M edges/s{pad}"
-          f"  (runs {runs[0]:.2f}..{runs[-1]:.2f} ms; {'graph' if use_graph else 'eager'})",
+          f"  (runs {runs[0]:.2f}..{runs[-1]:.2f} ms; {'graph' if use_graph else 'eager'};"
+          f" objective {OBJECTIVE})",
           flush=True)
     print(f"{'':34s} edge kernels, ms per eager step: {kt}", flush=True)
 
