@@ -387,7 +387,7 @@ int pfsgnn_mlp_bwd(const float* dY, int N, const float* Yp, const float* mu, con
                    void* stream);
 /* the same with SModel's node_mlp_2 backward (gnn.py:140-154) folded in:
  *   bn_part != NULL: the BatchNorm sums already made by the producer of dY
- *     (pfsgnn_target_bwd_bn's bn_part, bn_nparts = ceil(N / 64) per-block
+ *     (pfsgnn_target_bwd's bn_part, bn_nparts = ceil(N / 64) per-block
  *     partials [n][32]: sum dY in 0..16, sum dY*xhat in 16..32) instead of a
  *     sums launch of its own (gamma required);
  *   coef != NULL: dX rows [mom_k0, mom_k0 + 4 mom_c) -- d loss / d [mean; std;
@@ -593,10 +593,10 @@ int pfsgnn_rows_axpby(const float* g, const float* y, int C, long long N, const 
  * tensors are channel-major [C][EP] over these positions and hold 0 at padding.
  * Slices 4 q .. 4 q + 3 are the 4 waves of the blocks of 64-fiber group q =
  * g * ceil(NF/64) + (its group in graph g), each block taking one of KS step
- * splits, so the pfsgnn_sl_* edge ops below run the complete path's grid
- * shape and share its reductions; they take the same arguments and give the
- * same outputs as the complete-graph op of the same name (G, NF, NC: the
- * batch's graphs and per-graph node counts), plus the layout.  NC <= 128
+ * splits, so an edge op below given the layout (its `sl` field) runs the
+ * complete path's grid shape and shares its reductions; it takes the same
+ * arguments and gives the same outputs as on complete graphs (G, NF, NC: the
+ * batch's graphs and per-graph node counts).  NC <= 128
  * classes per graph; Fdim 8, 10, 16; the workspace of pfsgnn_workspace_bytes.
  * (Replaces torch_scatter.scatter, x[src], x[tgt] of gnn.py:100, 136-144,
  * 188-190 for such graphs, fused.) */
@@ -615,7 +615,7 @@ typedef struct {
  * the CU's 160 KB (e.g. 124 at Fdim 16 on the default path), and at most 128.
  * 0: no sliced kernels for this (F, path) -- the bf16 edge-state paths and
  * Fdims other than 8 / 10 / 16.  A batch above the limit runs the composed
- * general-graph ops (pfsgnn.sparse); the pfsgnn_sl_* ops refuse it.
+ * general-graph ops (pfsgnn.sparse); the edge ops and pfsgnn_sl_loss_* refuse it.
  * (Host-side query; it reads the kernels' attributes from the HIP runtime.) */
 int pfsgnn_sliced_max_nc(int F, int* nc);
 size_t pfsgnn_sliced_plan_ws_bytes(int G, int NF);
@@ -640,234 +640,179 @@ int pfsgnn_edges_from_slots(const float* y, const float* sc, const float* sh, lo
                             long long EP, int F, const int* pos_user, int rowmajor, float* dst,
                             void* stream);
 
-/* ---------------------------------------------------------------- edge ops */
+/* ---------------------------------------------------------------- edge ops
+ * One entry point per op: (const pfsgnn_<op>_args* a, ws, ws_bytes, stream).
+ * Every argument struct begins with G, NF, NC, F and `sl`: NULL for a batch of
+ * complete graphs, else the sliced general batch (above), whose edge tensors
+ * are [C][sl->EP], whose EdgeModel BatchNorm counts sl->E edges and whose
+ * `tmask` has pfsgnn_sl_tmask_bytes.  An optional part of an op is a group of
+ * fields left NULL / 0; which form runs is decided by which fields are set.
+ * Every argument check runs before the first launch. */
+#define PFSGNN_OP_EDGE_MLP_FWD 0
+#define PFSGNN_OP_SOURCE_FWD 1
+#define PFSGNN_OP_TARGET_FWD 2
+#define PFSGNN_OP_TARGET_BWD 3
+#define PFSGNN_OP_SOURCE_BWD 4
+#define PFSGNN_OP_EDGE_MLP_BWD 5
+/* sizeof the argument struct of op PFSGNN_OP_*, for bindings to check their
+ * struct layout; 0 for an unknown op */
+size_t pfsgnn_edge_args_bytes(int op);
 
 /* EdgeModel per-edge MLP (gnn.py:99-101 with the first Linear split):
  * z1 = Ps[:,f] + Pt[:,c] + W1[:,2F:3F] x ; y = W2 lrelu(z1) + b2, where
  * x = xsc*xe + xsh.  Also the batch moments mu/var (biased) of y. */
-int pfsgnn_edge_mlp_fwd(int G, int NF, int NC, int F, const float* xe, const float* xsc,
-                        const float* xsh, const float* Ps, const float* Pt, const float* W1,
-                        const float* W2, const float* b2, float* y, float* mu, float* var,
-                        void* ws, size_t ws_bytes, void* stream);
-/* the same + the double BatchNorm's finalize (pfsgnn_bn2_finalize's outputs
- * sc, sh, inv1, inv2 and running-stat updates) in the moments pass: the
- * EdgeModel training forward in one call (gnn.py:99-101) */
-int pfsgnn_edge_mlp_fwd_bn(int G, int NF, int NC, int F, const float* xe, const float* xsc,
-                           const float* xsh, const float* Ps, const float* Pt, const float* W1,
-                           const float* W2, const float* b2, float* y, float* mu, float* var,
-                           const float* gamma, const float* beta, float* rm, float* rv,
-                           float momentum, float eps, float* sc, float* sh, float* inv1,
-                           float* inv2, void* ws, size_t ws_bytes, void* stream);
+typedef struct {
+  int G, NF, NC, F;
+  const pfsgnn_sliced_t* sl;
+  const float *xe, *xsc, *xsh, *Ps, *Pt, *W1, *W2, *b2;
+  float *y, *mu, *var;
+  /* gamma != NULL: also the double BatchNorm's finalize (pfsgnn_bn2_finalize's
+   * outputs sc, sh, inv1, inv2 and running-stat updates) in the moments pass,
+   * the EdgeModel training forward in one call (gnn.py:99-101).  Needs beta,
+   * sc, sh, inv1, inv2; rm / rv both or neither. */
+  const float *gamma, *beta;
+  float *rm, *rv;
+  float momentum, eps;
+  float *sc, *sh, *inv1, *inv2;
+} pfsgnn_edge_mlp_fwd_args;
+int pfsgnn_edge_mlp_fwd(const pfsgnn_edge_mlp_fwd_args* a, void* ws, size_t ws_bytes,
+                        void* stream);
+
 /* SModel per-edge message + per-fiber centred moments (gnn.py:136-151).
  * mom [4][2F][NS]; hs [8F][NS] receives (mean, std, skew, kurt). */
-int pfsgnn_source_fwd(int G, int NF, int NC, int F, const float* y, const float* sc,
-                      const float* sh, const float* Qt, const float* Ws1, const float* Ws2,
-                      const float* bs2, float* mom, float* hs, void* ws, size_t ws_bytes,
-                      void* stream);
+typedef struct {
+  int G, NF, NC, F;
+  const pfsgnn_sliced_t* sl;
+  const float *y, *sc, *sh, *Qt, *Ws1, *Ws2, *bs2;
+  float *mom, *hs;
+  /* msg != NULL: also write the message cache (pfsgnn_msg_bytes; complete
+   * graphs only) */
+  float* msg;
+} pfsgnn_source_fwd_args;
+int pfsgnn_source_fwd(const pfsgnn_source_fwd_args* a, void* ws, size_t ws_bytes, void* stream);
 /* The SModel message cache (round 6): bytes of the per-edge messages m
  * [2F][E] (gnn.py:136, the output of node_mlp_1) that the current edge path
  * keeps between the forward and the backward -- complete graphs on the
  * PFSGNN_EDGE_MFMA / _MFMA_F32 paths when PFSGNN_MSG=1 is set, 0 otherwise
  * (the backward then recomputes them; the default: the forward's extra
- * 80 B per edge of writes cost more than the recompute).  pfsgnn_source_fwd_msg = pfsgnn_source_fwd + writes the
- * messages to `msg` (this many bytes); pfsgnn_source_bwd(_bn)_msg read them in
- * place of recomputing node_mlp_1's second Linear -- bit for bit the values the
- * forward computed, so results equal the recomputing calls'. */
+ * 80 B per edge of writes cost more than the recompute).
+ * pfsgnn_source_fwd given `msg` (this many bytes) writes the messages there;
+ * pfsgnn_source_bwd given the same buffer reads them in place of recomputing
+ * node_mlp_1's second Linear -- bit for bit the values the forward computed,
+ * so results equal the recomputing calls'. */
 size_t pfsgnn_msg_bytes(int G, int NF, int NC, int F);
-int pfsgnn_source_fwd_msg(int G, int NF, int NC, int F, const float* y, const float* sc,
-                          const float* sh, const float* Qt, const float* Ws1, const float* Ws2,
-                          const float* bs2, float* mom, float* hs, float* msg, void* ws,
-                          size_t ws_bytes, void* stream);
+
 /* TModel per-edge message, summed per class before its second Linear
- * (gnn.py:188-190): hsum[:,c] = sum_f lrelu(Rs[:,f] + Wt1[:,F:2F] x); with Wt2
- * (optional, [2F][2F]) also that Linear in the same call's reduction epilogue:
- * agg[:,c] = Wt2 hsum[:,c] + bscale*bt2. */
-int pfsgnn_target_fwd(int G, int NF, int NC, int F, const float* y, const float* sc,
-                      const float* sh, const float* Rs, const float* Wt1, float* hsum,
-                      const float* Wt2, const float* bt2, float bscale, float* agg,
-                      unsigned char* tmask, void* ws, size_t ws_bytes, void* stream);
+ * (gnn.py:188-190): hsum[:,c] = sum_f lrelu(Rs[:,f] + Wt1[:,F:2F] x). */
+typedef struct {
+  int G, NF, NC, F;
+  const pfsgnn_sliced_t* sl;
+  const float *y, *sc, *sh, *Rs, *Wt1;
+  float* hsum;
+  /* Wt2 != NULL ([2F][2F]; needs agg): also that Linear in the same call's
+   * reduction epilogue, agg[:,c] = Wt2 hsum[:,c] + bscale*bt2 */
+  const float *Wt2, *bt2;
+  float bscale;
+  float* agg;
+  unsigned char* tmask;   /* optional, pfsgnn_tmask_bytes below */
+} pfsgnn_target_fwd_args;
+int pfsgnn_target_fwd(const pfsgnn_target_fwd_args* a, void* ws, size_t ws_bytes, void* stream);
 /* Bytes of the TModel mask the current edge path keeps between the forward
  * and the backward (0: it keeps none, recomputes).  When non-zero and `tmask`
  * (this many bytes) is given to pfsgnn_target_fwd, the forward writes the
  * sign pattern of TModel's per-edge pre-activation (gnn.py:188, the LeakyReLU
- * of node_mlp_1) and pfsgnn_target_bwd / pfsgnn_source_bwd(_bn) given the
- * same buffer read it in place of recomputing that layer. */
+ * of node_mlp_1) and pfsgnn_target_bwd / pfsgnn_source_bwd given the same
+ * buffer read it in place of recomputing that layer. */
 size_t pfsgnn_tmask_bytes(int G, int NF, int NC, int F);
+size_t pfsgnn_sl_tmask_bytes(const pfsgnn_sliced_t* sl, int F);
+
 /* TModel edge backward: GzT[:,f] = sum_c g_z; dWt1[:,F:2F] += sum g_z x^T;
  * optional gxe = Wt1[:,F:2F]^T g_z (standalone TModel only); optional g_xs
  * += Wt1[:,0:F]^T GzT (the x_s[src] input gradient, in the reduction epilogue). */
-int pfsgnn_target_bwd(int G, int NF, int NC, int F, const float* y, const float* sc,
-                      const float* sh, const float* Rs, const float* Wt1, const float* g_hsum,
-                      float* GzT, float* dWt1, float* gxe, float* g_xs,
-                      const unsigned char* tmask, void* ws, size_t ws_bytes, void* stream);
-/* the same (complete graphs) where g_xs is final after this call and feeds
- * SModel's node_mlp_2 + BatchNorm backward (gnn.py:153-154): the epilogue
- * that finishes g_xs also writes that BatchNorm's backward sums over its
- * fibers, bn_part [ceil(G*NF / 64)][32] (sum g_xs, sum g_xs*(Yp - mu) /
- * sqrt(var + eps) per channel; bn_Yp [F][G*NF] the pre-norm output, bn_mu /
- * bn_var its batch statistics) for pfsgnn_mlp_bwd_pre. */
-int pfsgnn_target_bwd_bn(int G, int NF, int NC, int F, const float* y, const float* sc,
-                         const float* sh, const float* Rs, const float* Wt1, const float* g_hsum,
-                         float* GzT, float* dWt1, float* gxe, float* g_xs,
-                         const unsigned char* tmask, const float* bn_Yp, const float* bn_mu,
-                         const float* bn_var, float bn_eps, float* bn_part, void* ws,
-                         size_t ws_bytes, void* stream);
+typedef struct {
+  int G, NF, NC, F;
+  const pfsgnn_sliced_t* sl;
+  const float *y, *sc, *sh, *Rs, *Wt1, *g_hsum;
+  float *GzT, *dWt1, *gxe, *g_xs;
+  const unsigned char* tmask;
+  /* bn_part != NULL (complete graphs; needs g_xs, bn_Yp, bn_mu, bn_var): g_xs
+   * is final after this call and feeds SModel's node_mlp_2 + BatchNorm
+   * backward (gnn.py:153-154), so the epilogue that finishes g_xs also writes
+   * that BatchNorm's backward sums over its fibers, bn_part [ceil(G*NF / 64)][32]
+   * (sum g_xs, sum g_xs*(Yp - mu) / sqrt(var + eps) per channel; bn_Yp
+   * [F][G*NF] the pre-norm output, bn_mu / bn_var its batch statistics) for
+   * pfsgnn_mlp_bwd_pre */
+  const float *bn_Yp, *bn_mu, *bn_var;
+  float bn_eps;
+  float* bn_part;
+  int fold;   /* != 0: the first half of the folded pair (below) */
+} pfsgnn_target_bwd_args;
+int pfsgnn_target_bwd(const pfsgnn_target_bwd_args* a, void* ws, size_t ws_bytes, void* stream);
+
 /* SModel edge backward fused with TModel's per-edge input gradient, the
  * downstream edge gradient and the edge BatchNorm's two gradient sums:
  * g_tot = Ws1e^T g_zs + [Wt1e^T g_zt] + [g_next]; GzS per class;
- * dWs1[:,F:2F], dWs2, dbs2 accumulated; Sg/Sgx = sums of g_tot, g_tot*xhat
- * (xhat = (y-mu1)*inv1) when mu1 != NULL.  Rs/Wt1/g_hsum may be NULL.
+ * dWs1[:,F:2F], dWs2, dbs2 accumulated.  Rs/Wt1/g_hsum may be NULL (together).
  * Optional g_xt += Ws1[:,0:F]^T GzS (x_t[tgt] input gradient, reduction epilogue). */
-int pfsgnn_source_bwd(int G, int NF, int NC, int F, const float* y, const float* sc,
-                      const float* sh, const float* Qt, const float* Ws1, const float* Ws2,
-                      const float* bs2, const float* mean, const float* coef, const float* Rs,
-                      const float* Wt1, const float* g_hsum, const float* g_next,
-                      const float* mu1, const float* inv1, float* g_tot, float* GzS,
-                      float* dWs1, float* dWs2, float* dbs2, float* Sg, float* Sgx,
-                      float* g_xt, const unsigned char* tmask, void* ws, size_t ws_bytes,
-                      void* stream);
-/* the same with the edge BatchNorm's backward finished in the same call: in
- * place of Sg / Sgx it writes pfsgnn_bn2_bwd_coef's alpha, gam0, gam1 and
- * accumulates dgamma / dbeta (gamma, var1: that BatchNorm's weight and batch
- * variance; n = E) */
-int pfsgnn_source_bwd_bn(int G, int NF, int NC, int F, const float* y, const float* sc,
-                         const float* sh, const float* Qt, const float* Ws1, const float* Ws2,
-                         const float* bs2, const float* mean, const float* coef, const float* Rs,
-                         const float* Wt1, const float* g_hsum, const float* g_next,
-                         const float* mu1, const float* inv1, const float* var1,
-                         const float* gamma, long long n, float eps, float* g_tot, float* GzS,
-                         float* dWs1, float* dWs2, float* dbs2, float* alpha, float* gam0,
-                         float* gam1, float* dgamma, float* dbeta, float* g_xt,
-                         const unsigned char* tmask, void* ws, size_t ws_bytes, void* stream);
-/* pfsgnn_source_bwd / _bn with the forward's message cache (pfsgnn_msg_bytes) */
-int pfsgnn_source_bwd_msg(int G, int NF, int NC, int F, const float* y, const float* sc,
-                          const float* sh, const float* Qt, const float* Ws1, const float* Ws2,
-                          const float* bs2, const float* mean, const float* coef,
-                          const float* Rs, const float* Wt1, const float* g_hsum,
-                          const float* g_next, const float* mu1, const float* inv1,
-                          float* g_tot, float* GzS, float* dWs1, float* dWs2, float* dbs2,
-                          float* Sg, float* Sgx, float* g_xt, const unsigned char* tmask,
-                          const float* msg, void* ws, size_t ws_bytes, void* stream);
-int pfsgnn_source_bwd_bn_msg(int G, int NF, int NC, int F, const float* y, const float* sc,
-                             const float* sh, const float* Qt, const float* Ws1,
-                             const float* Ws2, const float* bs2, const float* mean,
-                             const float* coef, const float* Rs, const float* Wt1,
-                             const float* g_hsum, const float* g_next, const float* mu1,
-                             const float* inv1, const float* var1, const float* gamma,
-                             long long n, float eps, float* g_tot, float* GzS, float* dWs1,
-                             float* dWs2, float* dbs2, float* alpha, float* gam0, float* gam1,
-                             float* dgamma, float* dbeta, float* g_xt,
-                             const unsigned char* tmask, const float* msg, void* ws,
-                             size_t ws_bytes, void* stream);
+typedef struct {
+  int G, NF, NC, F;
+  const pfsgnn_sliced_t* sl;
+  const float *y, *sc, *sh, *Qt, *Ws1, *Ws2, *bs2, *mean, *coef, *Rs, *Wt1, *g_hsum, *g_next;
+  /* mu1 != NULL (needs inv1): the edge BatchNorm's backward, xhat = (y-mu1)*inv1.
+   * gamma == NULL: its two sums Sg / Sgx = sums of g_tot, g_tot*xhat (both
+   * required).  gamma != NULL (needs mu1, inv1, var1, n > 0, alpha, gam0, gam1,
+   * dgamma, dbeta; gamma, var1: that BatchNorm's weight and batch variance; n =
+   * E): finished in the same call -- in place of Sg / Sgx (unused) it writes
+   * pfsgnn_bn2_bwd_coef's alpha, gam0, gam1 and accumulates dgamma / dbeta */
+  const float *mu1, *inv1, *var1, *gamma;
+  long long n;
+  float eps;
+  float *g_tot, *GzS, *dWs1, *dWs2, *dbs2, *Sg, *Sgx, *alpha, *gam0, *gam1, *dgamma, *dbeta;
+  float* g_xt;
+  const unsigned char* tmask;
+  const float* msg;   /* the forward's message cache (pfsgnn_msg_bytes) or NULL */
+  float* dWt1;        /* != NULL: the second half of the folded pair (below) */
+} pfsgnn_source_bwd_args;
+int pfsgnn_source_bwd(const pfsgnn_source_bwd_args* a, void* ws, size_t ws_bytes, void* stream);
 /* The folded pair (complete graphs).  In training the engine wants no gxe
  * from TModel's edge backward, and source_bwd, one launch later, reloads the
  * same y rows and mask bytes and forms the same x and g_zt.  Where
  * pfsgnn_tbwd_fold(F) is 1 on the current edge path (the MFMA paths at Fdim 8
  * and 10; Fdim 16's source_bwd has no registers left for it),
- *   pfsgnn_target_bwd_fold (pfsgnn_target_bwd_bn's arguments; bn_part and its
- *     three inputs may all be NULL) with a mask and gxe == NULL runs a
- *     mask-only kernel: it reads tmask (4 bytes per edge) and g_hsum only and
- *     does NOT touch dWt1; GzT, g_xs and bn_part come out of the same
- *     reduction as before;
- *   pfsgnn_source_bwd_fold with dWt1 (tmask, Rs, Wt1, g_hsum required) also
- *     accumulates dWt1[:,F:2F] += g_zt x^T.  gamma != NULL: the edge BatchNorm
- *     coefficients as pfsgnn_source_bwd_bn (Sg / Sgx unused); gamma == NULL: Sg /
- *     Sgx as pfsgnn_source_bwd.  msg: the message cache or NULL.
- * Every output is bitwise that of pfsgnn_target_bwd_bn + pfsgnn_source_bwd_bn:
- * the same operations in the same order, issued from the other kernel.  A
- * caller gives pfsgnn_source_bwd_fold dWt1 exactly when the target call had a
- * mask and no gxe.  Where pfsgnn_tbwd_fold(F) is 0, or the target call has no
- * mask or wants gxe, both entry points run today's kernels (the target call
- * then accumulates dWt1[:,F:2F] itself and the source call ignores dWt1). */
+ *   pfsgnn_target_bwd with `fold`, a mask and gxe == NULL runs a mask-only
+ *     kernel: it reads tmask (4 bytes per edge) and g_hsum only and does NOT
+ *     touch dWt1; GzT, g_xs and bn_part come out of the same reduction as
+ *     before;
+ *   pfsgnn_source_bwd with dWt1 (tmask, Rs, Wt1, g_hsum required) also
+ *     accumulates dWt1[:,F:2F] += g_zt x^T.
+ * Every output is bitwise that of the two calls without fold / dWt1: the same
+ * operations in the same order, issued from the other kernel.  A caller gives
+ * pfsgnn_source_bwd dWt1 exactly when the target call had fold, a mask and no
+ * gxe.  Where pfsgnn_tbwd_fold(F) is 0, or the target call has no mask or
+ * wants gxe, both entry points run the unfolded kernels (the target call then
+ * accumulates dWt1[:,F:2F] itself and the source call ignores dWt1). */
 int pfsgnn_tbwd_fold(int F);
-int pfsgnn_target_bwd_fold(int G, int NF, int NC, int F, const float* y, const float* sc,
-                           const float* sh, const float* Rs, const float* Wt1,
-                           const float* g_hsum, float* GzT, float* dWt1, float* gxe, float* g_xs,
-                           const unsigned char* tmask, const float* bn_Yp, const float* bn_mu,
-                           const float* bn_var, float bn_eps, float* bn_part, void* ws,
-                           size_t ws_bytes, void* stream);
-int pfsgnn_source_bwd_fold(int G, int NF, int NC, int F, const float* y, const float* sc,
-                           const float* sh, const float* Qt, const float* Ws1, const float* Ws2,
-                           const float* bs2, const float* mean, const float* coef,
-                           const float* Rs, const float* Wt1, const float* g_hsum,
-                           const float* g_next, const float* mu1, const float* inv1,
-                           const float* var1, const float* gamma, long long n, float eps,
-                           float* g_tot, float* GzS, float* dWs1, float* dWs2, float* dbs2,
-                           float* Sg, float* Sgx, float* alpha, float* gam0, float* gam1,
-                           float* dgamma, float* dbeta, float* g_xt, const unsigned char* tmask,
-                           const float* msg, float* dWt1, void* ws, size_t ws_bytes,
-                           void* stream);
 /* Sg = sum g, Sgx = sum g*(y-mu1)*inv1 (standalone EdgeModel backward). */
 int pfsgnn_edge_bn_grad_sums(int G, int NF, int NC, int F, const float* g, const float* y,
                              const float* mu1, const float* inv1, float* Sg, float* Sgx,
                              void* ws, size_t ws_bytes, void* stream);
+
 /* EdgeModel per-edge MLP backward.  g_y = alpha*g_tot + gam0 + gam1*y;
  * gxe (optional) = W1[:,2F:3F]^T g_z1; GzEs [4F][NS], GzEt [4F][NT] are
  * the per-fiber / per-class sums of g_z1; dW1[:,2F:3F], dW2, db2 accumulated.
  * Optional, in the reductions' epilogues (gnn.py:100's node-input gradients):
  * g_xs += W1[:,0:F]^T GzEs, g_xt += W1[:,F:2F]^T GzEt, Vu [F][NT] =
  * W1[:,3F:4F]^T GzEt (the caller sums it per graph into g_u). */
-int pfsgnn_edge_mlp_bwd(int G, int NF, int NC, int F, const float* g_tot, const float* alpha,
-                        const float* gam0, const float* gam1, const float* y, const float* xe,
-                        const float* xsc, const float* xsh, const float* Ps, const float* Pt,
-                        const float* W1, const float* W2, float* dW1, float* dW2, float* db2,
-                        float* gxe, float* GzEs, float* GzEt, float* g_xs, float* g_xt,
-                        float* Vu, void* ws, size_t ws_bytes, void* stream);
-
-/* The edge ops above on a sliced general batch (pfsgnn_sliced_t): arguments
- * and outputs as the op of the same name; edge tensors are [C][sl->EP]; the
- * EdgeModel BatchNorm counts sl->E edges; `tmask` has pfsgnn_sl_tmask_bytes. */
-int pfsgnn_sl_edge_mlp_fwd(const pfsgnn_sliced_t* sl, int G, int NF, int NC, int F,
-                           const float* xe, const float* xsc, const float* xsh, const float* Ps,
-                           const float* Pt, const float* W1, const float* W2, const float* b2,
-                           float* y, float* mu, float* var, void* ws, size_t ws_bytes,
-                           void* stream);
-int pfsgnn_sl_edge_mlp_fwd_bn(const pfsgnn_sliced_t* sl, int G, int NF, int NC, int F,
-                              const float* xe, const float* xsc, const float* xsh,
-                              const float* Ps, const float* Pt, const float* W1, const float* W2,
-                              const float* b2, float* y, float* mu, float* var,
-                              const float* gamma, const float* beta, float* rm, float* rv,
-                              float momentum, float eps, float* sc, float* sh, float* inv1,
-                              float* inv2, void* ws, size_t ws_bytes, void* stream);
-int pfsgnn_sl_source_fwd(const pfsgnn_sliced_t* sl, int G, int NF, int NC, int F, const float* y,
-                         const float* sc, const float* sh, const float* Qt, const float* Ws1,
-                         const float* Ws2, const float* bs2, float* mom, float* hs, void* ws,
-                         size_t ws_bytes, void* stream);
-size_t pfsgnn_sl_tmask_bytes(const pfsgnn_sliced_t* sl, int F);
-int pfsgnn_sl_target_fwd(const pfsgnn_sliced_t* sl, int G, int NF, int NC, int F, const float* y,
-                         const float* sc, const float* sh, const float* Rs, const float* Wt1,
-                         float* hsum, const float* Wt2, const float* bt2, float bscale,
-                         float* agg, unsigned char* tmask, void* ws, size_t ws_bytes,
-                         void* stream);
-int pfsgnn_sl_target_bwd(const pfsgnn_sliced_t* sl, int G, int NF, int NC, int F, const float* y,
-                         const float* sc, const float* sh, const float* Rs, const float* Wt1,
-                         const float* g_hsum, float* GzT, float* dWt1, float* gxe, float* g_xs,
-                         const unsigned char* tmask, void* ws, size_t ws_bytes, void* stream);
-int pfsgnn_sl_source_bwd(const pfsgnn_sliced_t* sl, int G, int NF, int NC, int F, const float* y,
-                         const float* sc, const float* sh, const float* Qt, const float* Ws1,
-                         const float* Ws2, const float* bs2, const float* mean,
-                         const float* coef, const float* Rs, const float* Wt1,
-                         const float* g_hsum, const float* g_next, const float* mu1,
-                         const float* inv1, float* g_tot, float* GzS, float* dWs1, float* dWs2,
-                         float* dbs2, float* Sg, float* Sgx, float* g_xt,
-                         const unsigned char* tmask, void* ws, size_t ws_bytes, void* stream);
-int pfsgnn_sl_source_bwd_bn(const pfsgnn_sliced_t* sl, int G, int NF, int NC, int F,
-                            const float* y, const float* sc, const float* sh, const float* Qt,
-                            const float* Ws1, const float* Ws2, const float* bs2,
-                            const float* mean, const float* coef, const float* Rs,
-                            const float* Wt1, const float* g_hsum, const float* g_next,
-                            const float* mu1, const float* inv1, const float* var1,
-                            const float* gamma, long long n, float eps, float* g_tot, float* GzS,
-                            float* dWs1, float* dWs2, float* dbs2, float* alpha, float* gam0,
-                            float* gam1, float* dgamma, float* dbeta, float* g_xt,
-                            const unsigned char* tmask, void* ws, size_t ws_bytes, void* stream);
-int pfsgnn_sl_edge_mlp_bwd(const pfsgnn_sliced_t* sl, int G, int NF, int NC, int F,
-                           const float* g_tot, const float* alpha, const float* gam0,
-                           const float* gam1, const float* y, const float* xe, const float* xsc,
-                           const float* xsh, const float* Ps, const float* Pt, const float* W1,
-                           const float* W2, float* dW1, float* dW2, float* db2, float* gxe,
-                           float* GzEs, float* GzEt, float* g_xs, float* g_xt, float* Vu,
-                           void* ws, size_t ws_bytes, void* stream);
+typedef struct {
+  int G, NF, NC, F;
+  const pfsgnn_sliced_t* sl;
+  const float *g_tot, *alpha, *gam0, *gam1, *y, *xe, *xsc, *xsh, *Ps, *Pt, *W1, *W2;
+  float *dW1, *dW2, *db2, *gxe, *GzEs, *GzEt, *g_xs, *g_xt, *Vu;
+} pfsgnn_edge_mlp_bwd_args;
+int pfsgnn_edge_mlp_bwd(const pfsgnn_edge_mlp_bwd_args* a, void* ws, size_t ws_bytes,
+                        void* stream);
+/* Not available on a sliced batch (refused with an error text, before any
+ * launch): msg, bn_part, fold, dWt1. */
 
 /* ---------------------------------------------------------------- loss
  * train.py:29-80: decoder_e (gnn.py:307) + softplus + softfloor (train.py:21)

@@ -1635,14 +1635,31 @@ extern "C" size_t pfsgnn_workspace_bytes(int G, int NF, int NC, int F) {
   return (std::max(std::max(edge, node), lay) + 64 * 16) * sizeof(float) + 16 * 256;
 }
 
-static int edge_mlp_fwd_impl(const pfsgnn_sliced_t* sl, int G, int NF, int NC, int F,
-                             const float* xe, const float* xsc, const float* xsh, const float* Ps,
-                             const float* Pt, const float* W1, const float* W2, const float* b2,
-                             float* y, float* mu, float* var, Bn2Args bn, void* ws,
-                             size_t ws_bytes, void* stream) {
+extern "C" size_t pfsgnn_edge_args_bytes(int op) {
+  switch (op) {
+    case PFSGNN_OP_EDGE_MLP_FWD: return sizeof(pfsgnn_edge_mlp_fwd_args);
+    case PFSGNN_OP_SOURCE_FWD: return sizeof(pfsgnn_source_fwd_args);
+    case PFSGNN_OP_TARGET_FWD: return sizeof(pfsgnn_target_fwd_args);
+    case PFSGNN_OP_TARGET_BWD: return sizeof(pfsgnn_target_bwd_args);
+    case PFSGNN_OP_SOURCE_BWD: return sizeof(pfsgnn_source_bwd_args);
+    case PFSGNN_OP_EDGE_MLP_BWD: return sizeof(pfsgnn_edge_mlp_bwd_args);
+    default: return 0;
+  }
+}
+
+static int edge_mlp_fwd_impl(const pfsgnn_edge_mlp_fwd_args& a, void* ws, size_t ws_bytes,
+                             void* stream) {
+  const int G = a.G, NF = a.NF, NC = a.NC, F = a.F;
+  const pfsgnn_sliced_t* sl = a.sl;
   if (int rc = check_dims("pfsgnn_edge_mlp_fwd", G, NF, NC, F)) return rc;
+  PF_REQUIRE(a.xe && a.Ps && a.Pt && a.W1 && a.W2 && a.b2 && a.y && a.mu && a.var,
+             "pfsgnn_edge_mlp_fwd", "null");
+  PF_REQUIRE(!a.gamma || (a.beta && a.sc && a.sh && a.inv1 && a.inv2 && (!a.rm == !a.rv)),
+             "pfsgnn_edge_mlp_fwd", "gamma needs beta, sc, sh, inv1, inv2 (rm / rv both or neither)");
   if (int rc = check_sliced("pfsgnn_edge_mlp_fwd", sl, NC, F)) return rc;
-  PF_REQUIRE(xe && Ps && Pt && W1 && W2 && b2 && y && mu && var, "pfsgnn_edge_mlp_fwd", "null");
+  const Bn2Args bn = a.gamma ? Bn2Args{a.gamma, a.beta, a.rm, a.rv, a.momentum, a.eps, a.sc, a.sh,
+                                       a.inv1, a.inv2}
+                             : Bn2Args{};
   const EdgeGeo geo = geo_of(G, NF, NC, sl);
   Ws w{reinterpret_cast<char*>(ws), ws_bytes};
   hipStream_t st = as_stream(stream);
@@ -1652,12 +1669,12 @@ static int edge_mlp_fwd_impl(const pfsgnn_sliced_t* sl, int G, int NF, int NC, i
     { pf::Timer tm_("edge_mlp_fwd", st);
     float* tabs = w.take((size_t)pfm::sl_tab_floats(geo, F));
     PF_REQUIRE(tabs, "pfsgnn_edge_mlp_fwd", "workspace too small");
-    if (int rc = pfm::sl_edge_mlp_fwd(geo, sl_of(*sl), F, xe, xsc, xsh, Ps, Pt, W1, W2, b2, y, part,
-                                      tabs, mf_prec(0, F), st))
+    if (int rc = pfm::sl_edge_mlp_fwd(geo, sl_of(*sl), F, a.xe, a.xsc, a.xsh, a.Ps, a.Pt, a.W1, a.W2,
+                                      a.b2, a.y, part, tabs, mf_prec(0, F), st))
       return rc;
     tm_.end(); }
     hipLaunchKernelGGL(k_moments_finalize, dim3(F), dim3(256), 0, st, part, geo.nblocks, F, sl->E,
-                       mu, var, bn);
+                       a.mu, a.var, bn);
     return pf::check_launch("pfsgnn_edge_mlp_fwd");
   }
   if (use_mfma()) {
@@ -1668,81 +1685,38 @@ static int edge_mlp_fwd_impl(const pfsgnn_sliced_t* sl, int G, int NF, int NC, i
     if (geo.nblocks <= MOM_GROUP * MOM_MAXG && F <= 16) {
       unsigned* cnt = pf::sync_slot(1 + MOM_MAXG);
       double* gp = cnt ? reinterpret_cast<double*>(w.take(2 * 48 * MOM_MAXG)) : nullptr;
-      if (gp) fin = MomFin{cnt, gp, mu, var, geo.E, bn};
+      if (gp) fin = MomFin{cnt, gp, a.mu, a.var, geo.E, bn};
     }
     { pf::Timer tm_("edge_mlp_fwd", st);
     for (int rep = 0, nrep = 1 + pf::repeats("edge_mlp_fwd"); rep < nrep; ++rep) {
       MomFin fr = fin;   // (a timing repeat leaves the running statistics alone)
       if (rep + 1 < nrep) fr.bn.rm = fr.bn.rv = nullptr;
-      if (int rc = pfm::edge_mlp_fwd(geo, F, xe, xsc, xsh, Ps, Pt, W1, W2, b2, y, part, fr,
-                                     mf_prec(0, F), mf_bfy(), st))
+      if (int rc = pfm::edge_mlp_fwd(geo, F, a.xe, a.xsc, a.xsh, a.Ps, a.Pt, a.W1, a.W2, a.b2, a.y,
+                                     part, fr, mf_prec(0, F), mf_bfy(), st))
         return rc;
     }
     tm_.end(); }
     if (!fin.cnt)
       hipLaunchKernelGGL(k_moments_finalize, dim3(F), dim3(256), 0, st, part, geo.nblocks, F, geo.E,
-                         mu, var, bn);
+                         a.mu, a.var, bn);
     return pf::check_launch("pfsgnn_edge_mlp_fwd");
   }
-  const float* PtT = class_rows(Pt, 4 * F, geo, w, st);
-  const float* W2T = transposed(W2, F, 4 * F, w, st);
+  const float* PtT = class_rows(a.Pt, 4 * F, geo, w, st);
+  const float* W2T = transposed(a.W2, F, 4 * F, w, st);
   PF_REQUIRE(part && PtT && W2T, "pfsgnn_edge_mlp_fwd", "workspace too small");
   { pf::Timer tm_("edge_mlp_fwd", st);
   DISPATCH_F(F, hipLaunchKernelGGL(k_edge_mlp_fwd<FF>, dim3(edge_grid(geo)), dim3(256), 0, st, geo,
-                                   xe, xsc, xsh, Ps, PtT, W1, W2T, b2, y, part));
+                                   a.xe, a.xsc, a.xsh, a.Ps, PtT, a.W1, W2T, a.b2, a.y, part));
   tm_.end(); }
   hipLaunchKernelGGL(k_moments_finalize, dim3(F), dim3(256), 0, st, part, geo.nblocks, F, geo.E,
-                     mu, var, bn);
+                     a.mu, a.var, bn);
   return pf::check_launch("pfsgnn_edge_mlp_fwd");
 }
 
-extern "C" int pfsgnn_edge_mlp_fwd(int G, int NF, int NC, int F, const float* xe,
-                                   const float* xsc, const float* xsh, const float* Ps,
-                                   const float* Pt, const float* W1, const float* W2,
-                                   const float* b2, float* y, float* mu, float* var, void* ws,
-                                   size_t ws_bytes, void* stream) {
-  return edge_mlp_fwd_impl(nullptr, G, NF, NC, F, xe, xsc, xsh, Ps, Pt, W1, W2, b2, y, mu, var,
-                           Bn2Args{}, ws, ws_bytes, stream);
-}
-
-extern "C" int pfsgnn_edge_mlp_fwd_bn(int G, int NF, int NC, int F, const float* xe,
-                                      const float* xsc, const float* xsh, const float* Ps,
-                                      const float* Pt, const float* W1, const float* W2,
-                                      const float* b2, float* y, float* mu, float* var,
-                                      const float* gamma, const float* beta, float* rm, float* rv,
-                                      float momentum, float eps, float* sc, float* sh,
-                                      float* inv1, float* inv2, void* ws, size_t ws_bytes,
-                                      void* stream) {
-  PF_REQUIRE(gamma && beta && sc && sh && inv1 && inv2 && (!rm == !rv),
-             "pfsgnn_edge_mlp_fwd_bn", "null");
-  return edge_mlp_fwd_impl(nullptr, G, NF, NC, F, xe, xsc, xsh, Ps, Pt, W1, W2, b2, y, mu, var,
-                           Bn2Args{gamma, beta, rm, rv, momentum, eps, sc, sh, inv1, inv2}, ws,
-                           ws_bytes, stream);
-}
-
-extern "C" int pfsgnn_sl_edge_mlp_fwd(const pfsgnn_sliced_t* sl, int G, int NF, int NC, int F,
-                                      const float* xe, const float* xsc, const float* xsh,
-                                      const float* Ps, const float* Pt, const float* W1,
-                                      const float* W2, const float* b2, float* y, float* mu,
-                                      float* var, void* ws, size_t ws_bytes, void* stream) {
-  PF_REQUIRE(sl, "pfsgnn_sl_edge_mlp_fwd", "null layout");
-  return edge_mlp_fwd_impl(sl, G, NF, NC, F, xe, xsc, xsh, Ps, Pt, W1, W2, b2, y, mu, var,
-                           Bn2Args{}, ws, ws_bytes, stream);
-}
-
-extern "C" int pfsgnn_sl_edge_mlp_fwd_bn(const pfsgnn_sliced_t* sl, int G, int NF, int NC, int F,
-                                         const float* xe, const float* xsc, const float* xsh,
-                                         const float* Ps, const float* Pt, const float* W1,
-                                         const float* W2, const float* b2, float* y, float* mu,
-                                         float* var, const float* gamma, const float* beta,
-                                         float* rm, float* rv, float momentum, float eps,
-                                         float* sc, float* sh, float* inv1, float* inv2, void* ws,
-                                         size_t ws_bytes, void* stream) {
-  PF_REQUIRE(sl && gamma && beta && sc && sh && inv1 && inv2 && (!rm == !rv),
-             "pfsgnn_sl_edge_mlp_fwd_bn", "null");
-  return edge_mlp_fwd_impl(sl, G, NF, NC, F, xe, xsc, xsh, Ps, Pt, W1, W2, b2, y, mu, var,
-                           Bn2Args{gamma, beta, rm, rv, momentum, eps, sc, sh, inv1, inv2}, ws,
-                           ws_bytes, stream);
+extern "C" int pfsgnn_edge_mlp_fwd(const pfsgnn_edge_mlp_fwd_args* a, void* ws, size_t ws_bytes,
+                                   void* stream) {
+  PF_REQUIRE(a, "pfsgnn_edge_mlp_fwd", "null arguments");
+  return pf::take_pending(edge_mlp_fwd_impl(*a, ws, ws_bytes, stream));
 }
 
 // The SModel message cache (pfsgnn_msg_bytes): available on the complete-graph
@@ -1768,16 +1742,16 @@ static size_t msg_bytes(int G, int NF, int NC, int F) {
 }
 extern "C" size_t pfsgnn_msg_bytes(int G, int NF, int NC, int F) { return msg_bytes(G, NF, NC, F); }
 
-static int source_fwd_impl(const pfsgnn_sliced_t* sl, int G, int NF, int NC, int F,
-                           const float* y, const float* sc, const float* sh, const float* Qt,
-                           const float* Ws1, const float* Ws2, const float* bs2, float* mom,
-                           float* hs, void* ws, size_t ws_bytes, void* stream,
-                           float* msg = nullptr) {
+static int source_fwd_impl(const pfsgnn_source_fwd_args& a, void* ws, size_t ws_bytes,
+                           void* stream) {
+  const int G = a.G, NF = a.NF, NC = a.NC, F = a.F;
+  const pfsgnn_sliced_t* sl = a.sl;
   if (int rc = check_dims("pfsgnn_source_fwd", G, NF, NC, F)) return rc;
-  PF_REQUIRE(!msg || (!sl && msg_bytes(G, NF, NC, F) > 0), "pfsgnn_source_fwd_msg",
-             "the message cache is not kept on this path (pfsgnn_msg_bytes is 0)");
+  PF_REQUIRE(!(sl && a.msg), "pfsgnn_source_fwd", "sl with msg: no message cache on a sliced batch");
+  PF_REQUIRE(!a.msg || msg_bytes(G, NF, NC, F) > 0, "pfsgnn_source_fwd",
+             "msg: the message cache is not kept on this path (pfsgnn_msg_bytes is 0)");
+  PF_REQUIRE(a.y && a.Qt && a.Ws1 && a.Ws2 && a.bs2 && a.mom && a.hs, "pfsgnn_source_fwd", "null");
   if (int rc = check_sliced("pfsgnn_source_fwd", sl, NC, F)) return rc;
-  PF_REQUIRE(y && Qt && Ws1 && Ws2 && bs2 && mom && hs, "pfsgnn_source_fwd", "null");
   const EdgeGeo geo = geo_of(G, NF, NC, sl);
   const int C = 2 * F;
   Ws w{reinterpret_cast<char*>(ws), ws_bytes};
@@ -1786,8 +1760,8 @@ static int source_fwd_impl(const pfsgnn_sliced_t* sl, int G, int NF, int NC, int
     pf::Timer tm_("source_fwd", st);
     float* tabs = w.take((size_t)pfm::sl_tab_floats(geo, F));
     PF_REQUIRE(tabs, "pfsgnn_source_fwd", "workspace too small");
-    if (int rc = pfm::sl_source_fwd(geo, sl_of(*sl), F, y, sc, sh, Qt, Ws1, Ws2, bs2, mom, hs, tabs,
-                                    mf_prec(1, F), st))
+    if (int rc = pfm::sl_source_fwd(geo, sl_of(*sl), F, a.y, a.sc, a.sh, a.Qt, a.Ws1, a.Ws2, a.bs2,
+                                    a.mom, a.hs, tabs, mf_prec(1, F), st))
       return rc;
     tm_.end();
     return pf::check_launch("pfsgnn_source_fwd");
@@ -1795,8 +1769,8 @@ static int source_fwd_impl(const pfsgnn_sliced_t* sl, int G, int NF, int NC, int
   if (use_mfma() && NC <= 256 && sfwd_tiles()) {
     pf::Timer tm_("source_fwd", st);
     for (int rep = 0, nrep = 1 + pf::repeats("source_fwd"); rep < nrep; ++rep)
-      if (int rc = pfm::source_fwd_tiles(geo, F, y, sc, sh, Qt, Ws1, Ws2, bs2, mom, hs, msg,
-                                         mf_prec(1, F), sfwd_wave_nc(), st))
+      if (int rc = pfm::source_fwd_tiles(geo, F, a.y, a.sc, a.sh, a.Qt, a.Ws1, a.Ws2, a.bs2, a.mom,
+                                         a.hs, a.msg, mf_prec(1, F), sfwd_wave_nc(), st))
         return rc;
     tm_.end();
     return pf::check_launch("pfsgnn_source_fwd");
@@ -1805,50 +1779,29 @@ static int source_fwd_impl(const pfsgnn_sliced_t* sl, int G, int NF, int NC, int
   if (use_mfma()) {
     PF_REQUIRE(partS, "pfsgnn_source_fwd", "workspace too small");
     pf::Timer tm_("source_fwd", st);
-    if (int rc = pfm::source_fwd(geo, F, y, sc, sh, Qt, Ws1, Ws2, bs2, partS, mf_prec(1, F), st))
+    if (int rc = pfm::source_fwd(geo, F, a.y, a.sc, a.sh, a.Qt, a.Ws1, a.Ws2, a.bs2, partS,
+                                   mf_prec(1, F), st))
       return rc;
     tm_.end();
   } else {
-  const float* QtT = class_rows(Qt, C, geo, w, st);
-  const float* Ws2T = transposed(Ws2, C, C, w, st);
+  const float* QtT = class_rows(a.Qt, C, geo, w, st);
+  const float* Ws2T = transposed(a.Ws2, C, C, w, st);
   PF_REQUIRE(partS && QtT && Ws2T, "pfsgnn_source_fwd", "workspace too small");
   { pf::Timer tm_("source_fwd", st);
-  DISPATCH_F(F, hipLaunchKernelGGL(k_source_fwd<FF>, dim3(edge_grid(geo)), dim3(256), 0, st, geo, y,
-                                   sc, sh, QtT, Ws1, Ws2T, bs2, partS));
+  DISPATCH_F(F, hipLaunchKernelGGL(k_source_fwd<FF>, dim3(edge_grid(geo)), dim3(256), 0, st, geo,
+                                   a.y, a.sc, a.sh, QtT, a.Ws1, Ws2T, a.bs2, partS));
   tm_.end(); }
   }
   const long long len = (long long)C * geo.NS;
   hipLaunchKernelGGL(k_source_finalize, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, st,
-                     partS, geo.KS, geo.CPS, C, geo.NS, NC, mom, hs);
+                     partS, geo.KS, geo.CPS, C, geo.NS, NC, a.mom, a.hs);
   return pf::check_launch("pfsgnn_source_fwd");
 }
 
-extern "C" int pfsgnn_source_fwd(int G, int NF, int NC, int F, const float* y, const float* sc,
-                                 const float* sh, const float* Qt, const float* Ws1,
-                                 const float* Ws2, const float* bs2, float* mom, float* hs,
-                                 void* ws, size_t ws_bytes, void* stream) {
-  return source_fwd_impl(nullptr, G, NF, NC, F, y, sc, sh, Qt, Ws1, Ws2, bs2, mom, hs, ws,
-                         ws_bytes, stream);
-}
-
-extern "C" int pfsgnn_source_fwd_msg(int G, int NF, int NC, int F, const float* y,
-                                     const float* sc, const float* sh, const float* Qt,
-                                     const float* Ws1, const float* Ws2, const float* bs2,
-                                     float* mom, float* hs, float* msg, void* ws, size_t ws_bytes,
-                                     void* stream) {
-  PF_REQUIRE(msg, "pfsgnn_source_fwd_msg", "null message cache");
-  return source_fwd_impl(nullptr, G, NF, NC, F, y, sc, sh, Qt, Ws1, Ws2, bs2, mom, hs, ws,
-                         ws_bytes, stream, msg);
-}
-
-extern "C" int pfsgnn_sl_source_fwd(const pfsgnn_sliced_t* sl, int G, int NF, int NC, int F,
-                                    const float* y, const float* sc, const float* sh,
-                                    const float* Qt, const float* Ws1, const float* Ws2,
-                                    const float* bs2, float* mom, float* hs, void* ws,
-                                    size_t ws_bytes, void* stream) {
-  PF_REQUIRE(sl, "pfsgnn_sl_source_fwd", "null layout");
-  return source_fwd_impl(sl, G, NF, NC, F, y, sc, sh, Qt, Ws1, Ws2, bs2, mom, hs, ws, ws_bytes,
-                         stream);
+extern "C" int pfsgnn_source_fwd(const pfsgnn_source_fwd_args* a, void* ws, size_t ws_bytes,
+                                 void* stream) {
+  PF_REQUIRE(a, "pfsgnn_source_fwd", "null arguments");
+  return pf::take_pending(source_fwd_impl(*a, ws, ws_bytes, stream));
 }
 
 extern "C" size_t pfsgnn_tmask_bytes(int G, int NF, int NC, int F) {
@@ -1886,34 +1839,34 @@ static int target_fwd_edges(const pfsgnn_sliced_t* sl, const EdgeGeo& geo, int F
   return 0;
 }
 
-static int target_fwd_impl(const pfsgnn_sliced_t* sl, int G, int NF, int NC, int F,
-                           const float* y, const float* sc, const float* sh, const float* Rs,
-                           const float* Wt1, float* hsum, const float* Wt2, const float* bt2,
-                           float bscale, float* agg, unsigned char* tmask, void* ws,
-                           size_t ws_bytes, void* stream) {
+static int target_fwd_impl(const pfsgnn_target_fwd_args& a, void* ws, size_t ws_bytes,
+                           void* stream) {
+  const int G = a.G, NF = a.NF, NC = a.NC, F = a.F;
+  const pfsgnn_sliced_t* sl = a.sl;
   if (int rc = check_dims("pfsgnn_target_fwd", G, NF, NC, F)) return rc;
+  PF_REQUIRE(a.y && a.Rs && a.Wt1 && a.hsum, "pfsgnn_target_fwd", "null");
+  PF_REQUIRE(!a.Wt2 || a.agg, "pfsgnn_target_fwd", "Wt2 needs agg");
   if (int rc = check_sliced("pfsgnn_target_fwd", sl, NC, F)) return rc;
-  PF_REQUIRE(y && Rs && Wt1 && hsum, "pfsgnn_target_fwd", "null");
   const EdgeGeo geo = geo_of(G, NF, NC, sl);
   Ws w{reinterpret_cast<char*>(ws), ws_bytes};
   float* part = w.take((size_t)G * col_bpg(geo, sl) * NC * 2 * F);
   PF_REQUIRE(part, "pfsgnn_target_fwd", "workspace too small");
   hipStream_t st = as_stream(stream);
-  if (int rc = target_fwd_edges(sl, geo, F, y, sc, sh, Rs, Wt1, part, tmask, st)) return rc;
-  PF_REQUIRE(!Wt2 || agg, "pfsgnn_target_fwd", "Wt2 needs agg");
+  if (int rc = target_fwd_edges(sl, geo, F, a.y, a.sc, a.sh, a.Rs, a.Wt1, part, a.tmask, st))
+    return rc;
   // agg = Wt2 hsum + bscale bt2 (gnn.py:188-190, the second Linear after the sum)
-  const NodeLin La = Wt2 ? NodeLin{Wt2, 2 * F, 0, 2 * F, 0, bt2, bscale, agg, (long long)G * NC}
-                         : no_lin();
-  if (int rc = columns_lin(part, G, col_bpg(geo, sl), NC, 2 * F, hsum, La, no_lin(), st)) return rc;
+  const NodeLin La = a.Wt2 ? NodeLin{a.Wt2, 2 * F, 0, 2 * F, 0, a.bt2, a.bscale, a.agg,
+                                     (long long)G * NC}
+                           : no_lin();
+  if (int rc = columns_lin(part, G, col_bpg(geo, sl), NC, 2 * F, a.hsum, La, no_lin(), st))
+    return rc;
   return pf::check_launch("pfsgnn_target_fwd");
 }
 
-extern "C" int pfsgnn_target_fwd(int G, int NF, int NC, int F, const float* y, const float* sc,
-                                 const float* sh, const float* Rs, const float* Wt1, float* hsum,
-                                 const float* Wt2, const float* bt2, float bscale, float* agg,
-                                 unsigned char* tmask, void* ws, size_t ws_bytes, void* stream) {
-  return target_fwd_impl(nullptr, G, NF, NC, F, y, sc, sh, Rs, Wt1, hsum, Wt2, bt2, bscale, agg,
-                         tmask, ws, ws_bytes, stream);
+extern "C" int pfsgnn_target_fwd(const pfsgnn_target_fwd_args* a, void* ws, size_t ws_bytes,
+                                 void* stream) {
+  PF_REQUIRE(a, "pfsgnn_target_fwd", "null arguments");
+  return pf::take_pending(target_fwd_impl(*a, ws, ws_bytes, stream));
 }
 
 extern "C" size_t pfsgnn_block_tail_bytes(void) { return sizeof(pfsgnn_block_tail); }
@@ -1947,28 +1900,31 @@ extern "C" int pfsgnn_target_block_fwd(const pfsgnn_block_tail* a, void* ws, siz
   return pf::check_launch(where);
 }
 
-extern "C" int pfsgnn_sl_target_fwd(const pfsgnn_sliced_t* sl, int G, int NF, int NC, int F,
-                                    const float* y, const float* sc, const float* sh,
-                                    const float* Rs, const float* Wt1, float* hsum,
-                                    const float* Wt2, const float* bt2, float bscale, float* agg,
-                                    unsigned char* tmask, void* ws, size_t ws_bytes,
-                                    void* stream) {
-  PF_REQUIRE(sl, "pfsgnn_sl_target_fwd", "null layout");
-  return target_fwd_impl(sl, G, NF, NC, F, y, sc, sh, Rs, Wt1, hsum, Wt2, bt2, bscale, agg, tmask,
-                         ws, ws_bytes, stream);
-}
+// The folded pair (include/pfsgnn.h): where the edge path's source_bwd also
+// takes TModel's edge weight gradient (pfm::source_bwd_folds), target_bwd with
+// `fold`, the forward's mask and no edge-input gradient runs its mask-only
+// form (km_target_bwd's NW) and leaves dWt1[:, F:2F] to source_bwd's dWt1.
+static bool tbwd_folds(int F) { return use_mfma() && pfm::source_bwd_folds(F, mf_prec(1, F)); }
 
-static int target_bwd_impl(const pfsgnn_sliced_t* sl, int G, int NF, int NC, int F,
-                           const float* y, const float* sc, const float* sh, const float* Rs,
-                           const float* Wt1, const float* g_hsum, float* GzT, float* dWt1,
-                           float* gxe, float* g_xs, const unsigned char* tmask, void* ws,
-                           size_t ws_bytes, void* stream,
-                           const FiberBnSums& bs = FiberBnSums{}, bool fold = false) {
-  // fold (pfsgnn_target_bwd_fold): the mask-only kernel, no weight-gradient
-  // partial and no reduction into dWt1 -- source_bwd takes dWt1[:, F:2F]
+extern "C" int pfsgnn_tbwd_fold(int F) { return tbwd_folds(F) ? 1 : 0; }
+
+static int target_bwd_impl(const pfsgnn_target_bwd_args& a, void* ws, size_t ws_bytes,
+                           void* stream) {
+  const int G = a.G, NF = a.NF, NC = a.NC, F = a.F;
+  const pfsgnn_sliced_t* sl = a.sl;
   if (int rc = check_dims("pfsgnn_target_bwd", G, NF, NC, F)) return rc;
+  PF_REQUIRE(!(sl && a.bn_part), "pfsgnn_target_bwd",
+             "sl with bn_part: no fiber BatchNorm sums on a sliced batch");
+  PF_REQUIRE(!(sl && a.fold), "pfsgnn_target_bwd", "sl with fold: no folded pair on a sliced batch");
+  PF_REQUIRE(a.y && a.Rs && a.Wt1 && a.g_hsum && a.GzT && a.dWt1, "pfsgnn_target_bwd", "null");
+  PF_REQUIRE(!a.bn_part || (a.g_xs && a.bn_Yp && a.bn_mu && a.bn_var), "pfsgnn_target_bwd",
+             "bn_part: the BatchNorm sums need g_xs, bn_Yp, bn_mu, bn_var");
   if (int rc = check_sliced("pfsgnn_target_bwd", sl, NC, F)) return rc;
-  PF_REQUIRE(y && Rs && Wt1 && g_hsum && GzT && dWt1, "pfsgnn_target_bwd", "null");
+  const FiberBnSums bs = a.bn_part ? FiberBnSums{a.bn_Yp, a.bn_mu, a.bn_var, a.bn_eps, a.bn_part}
+                                   : FiberBnSums{};
+  // fold: the mask-only kernel, no weight-gradient partial and no reduction
+  // into dWt1 -- source_bwd takes dWt1[:, F:2F]
+  const bool fold = a.fold && a.tmask && !a.gxe && tbwd_folds(F);
   const EdgeGeo geo = geo_of(G, NF, NC, sl);
   const int C = 2 * F;
   Ws w{reinterpret_cast<char*>(ws), ws_bytes};
@@ -1976,93 +1932,44 @@ static int target_bwd_impl(const pfsgnn_sliced_t* sl, int G, int NF, int NC, int
   float* part = fold ? nullptr : pf::defer_take((size_t)geo.nblocks * C * F);
   const bool defer = part != nullptr;
   if (!defer && !fold) part = w.take((size_t)geo.nblocks * C * F);
-  float* gz = fiber_dst(geo, C, GzT, w);
-  const float* ghT = (sl || use_mfma()) ? g_hsum
-                                       : class_rows(g_hsum, C, geo, w, st);
+  float* gz = fiber_dst(geo, C, a.GzT, w);
+  const float* ghT = (sl || use_mfma()) ? a.g_hsum
+                                       : class_rows(a.g_hsum, C, geo, w, st);
   PF_REQUIRE((part || fold) && gz && ghT, "pfsgnn_target_bwd", "workspace too small");
   { pf::Timer tm_("target_bwd", st);
   if (sl) {
     float* tabs = w.take((size_t)pfm::sl_tab_floats(geo, F));
     PF_REQUIRE(tabs, "pfsgnn_target_bwd", "workspace too small");
-    if (int rc = pfm::sl_target_bwd(geo, sl_of(*sl), F, y, sc, sh, Rs, Wt1, ghT, gz, gxe, part,
-                                    tmask, tabs, mf_prec(1, F), st))
+    if (int rc = pfm::sl_target_bwd(geo, sl_of(*sl), F, a.y, a.sc, a.sh, a.Rs, a.Wt1, ghT, gz,
+                                    a.gxe, part, a.tmask, tabs, mf_prec(1, F), st))
       return rc;
   } else if (use_mfma()) {
     for (int rep = 0, nrep = 1 + pf::repeats("target_bwd"); rep < nrep; ++rep)
-      if (int rc = pfm::target_bwd(geo, F, y, sc, sh, Rs, Wt1, ghT, gz, gxe, part, tmask,
-                                   mf_prec(1, F), st))
+      if (int rc = pfm::target_bwd(geo, F, a.y, a.sc, a.sh, a.Rs, a.Wt1, ghT, gz, a.gxe, part,
+                                   a.tmask, mf_prec(1, F), st))
         return rc;
   } else {
-  DISPATCH_F(F, hipLaunchKernelGGL(k_target_bwd<FF>, dim3(edge_grid(geo)), dim3(256), 0, st, geo, y,
-                                   sc, sh, Rs, Wt1, ghT, gz, gxe, part));
+  DISPATCH_F(F, hipLaunchKernelGGL(k_target_bwd<FF>, dim3(edge_grid(geo)), dim3(256), 0, st, geo,
+                                   a.y, a.sc, a.sh, a.Rs, a.Wt1, ghT, gz, a.gxe, part));
   }
   tm_.end(); }
   // g_xs += Wt1[:, 0:F]^T GzT (gnn.py:188, the x_s[src] input gradient)
-  if (int rc = fiber_finish_lin(geo, C, gz, GzT, lin_t_add(g_xs ? Wt1 : nullptr, 2 * F, 0, F, g_xs,
-                                                           geo.NS),
+  if (int rc = fiber_finish_lin(geo, C, gz, a.GzT,
+                                lin_t_add(a.g_xs ? a.Wt1 : nullptr, 2 * F, 0, F, a.g_xs, geo.NS),
                                 no_lin(), st, bs))
     return rc;
   if (!fold) {
-    const RedDesc rd{part, geo.nblocks, (size_t)C * F, F, C, F, dWt1 + F, C, 1, 1.f};
+    const RedDesc rd{part, geo.nblocks, (size_t)C * F, F, C, F, a.dWt1 + F, C, 1, 1.f};
     if (defer) pf::defer_push(&rd, 1);
     else launch_reduce_multi(&rd, 1, st);
   }
   return pf::check_launch("pfsgnn_target_bwd");
 }
 
-extern "C" int pfsgnn_target_bwd(int G, int NF, int NC, int F, const float* y, const float* sc,
-                                 const float* sh, const float* Rs, const float* Wt1,
-                                 const float* g_hsum, float* GzT, float* dWt1, float* gxe,
-                                 float* g_xs, const unsigned char* tmask, void* ws,
-                                 size_t ws_bytes, void* stream) {
-  return target_bwd_impl(nullptr, G, NF, NC, F, y, sc, sh, Rs, Wt1, g_hsum, GzT, dWt1, gxe, g_xs,
-                         tmask, ws, ws_bytes, stream);
-}
-
-extern "C" int pfsgnn_target_bwd_bn(int G, int NF, int NC, int F, const float* y,
-                                    const float* sc, const float* sh, const float* Rs,
-                                    const float* Wt1, const float* g_hsum, float* GzT, float* dWt1,
-                                    float* gxe, float* g_xs, const unsigned char* tmask,
-                                    const float* bn_Yp, const float* bn_mu, const float* bn_var,
-                                    float bn_eps, float* bn_part, void* ws, size_t ws_bytes,
-                                    void* stream) {
-  PF_REQUIRE(g_xs && bn_Yp && bn_mu && bn_var && bn_part, "pfsgnn_target_bwd_bn", "null");
-  return target_bwd_impl(nullptr, G, NF, NC, F, y, sc, sh, Rs, Wt1, g_hsum, GzT, dWt1, gxe, g_xs,
-                         tmask, ws, ws_bytes, stream,
-                         FiberBnSums{bn_Yp, bn_mu, bn_var, bn_eps, bn_part});
-}
-
-// The folded pair (include/pfsgnn.h): where the edge path's source_bwd also
-// takes TModel's edge weight gradient (pfm::source_bwd_folds), target_bwd with
-// the forward's mask and no edge-input gradient runs its mask-only form
-// (km_target_bwd's NW) and leaves dWt1[:, F:2F] to pfsgnn_source_bwd_fold.
-static bool tbwd_folds(int F) { return use_mfma() && pfm::source_bwd_folds(F, mf_prec(1, F)); }
-
-extern "C" int pfsgnn_tbwd_fold(int F) { return tbwd_folds(F) ? 1 : 0; }
-
-extern "C" int pfsgnn_target_bwd_fold(int G, int NF, int NC, int F, const float* y,
-                                      const float* sc, const float* sh, const float* Rs,
-                                      const float* Wt1, const float* g_hsum, float* GzT,
-                                      float* dWt1, float* gxe, float* g_xs,
-                                      const unsigned char* tmask, const float* bn_Yp,
-                                      const float* bn_mu, const float* bn_var, float bn_eps,
-                                      float* bn_part, void* ws, size_t ws_bytes, void* stream) {
-  PF_REQUIRE(!bn_part || (g_xs && bn_Yp && bn_mu && bn_var), "pfsgnn_target_bwd_fold",
-             "BatchNorm sums need g_xs, Yp, mu, var");
-  const FiberBnSums bs = bn_part ? FiberBnSums{bn_Yp, bn_mu, bn_var, bn_eps, bn_part} : FiberBnSums{};
-  return target_bwd_impl(nullptr, G, NF, NC, F, y, sc, sh, Rs, Wt1, g_hsum, GzT, dWt1, gxe, g_xs,
-                         tmask, ws, ws_bytes, stream, bs, tmask && !gxe && tbwd_folds(F));
-}
-
-extern "C" int pfsgnn_sl_target_bwd(const pfsgnn_sliced_t* sl, int G, int NF, int NC, int F,
-                                    const float* y, const float* sc, const float* sh,
-                                    const float* Rs, const float* Wt1, const float* g_hsum,
-                                    float* GzT, float* dWt1, float* gxe, float* g_xs,
-                                    const unsigned char* tmask, void* ws, size_t ws_bytes,
-                                    void* stream) {
-  PF_REQUIRE(sl, "pfsgnn_sl_target_bwd", "null layout");
-  return target_bwd_impl(sl, G, NF, NC, F, y, sc, sh, Rs, Wt1, g_hsum, GzT, dWt1, gxe, g_xs, tmask,
-                         ws, ws_bytes, stream);
+extern "C" int pfsgnn_target_bwd(const pfsgnn_target_bwd_args* a, void* ws, size_t ws_bytes,
+                                 void* stream) {
+  PF_REQUIRE(a, "pfsgnn_target_bwd", "null arguments");
+  return pf::take_pending(target_bwd_impl(*a, ws, ws_bytes, stream));
 }
 
 // The edge BatchNorm's two gradient sums straight from source_bwd's block
@@ -2136,164 +2043,40 @@ __global__ __launch_bounds__(256) void k_bn2_coef_columns_lin(const float* __res
     reduce_columns_lin_block<C>(S, bx - F, cr.part, cr.G, cr.BPG, cr.NC, cr.out, cr.L0, cr.L1);
 }
 
-static int source_bwd_impl(const pfsgnn_sliced_t* sl, int G, int NF, int NC, int F,
-                           const float* y, const float* sc, const float* sh, const float* Qt,
-                           const float* Ws1, const float* Ws2, const float* bs2, const float* mean,
-                           const float* coef, const float* Rs, const float* Wt1,
-                           const float* g_hsum, const float* g_next, const float* mu1,
-                           const float* inv1, float* g_tot, float* GzS, float* dWs1, float* dWs2,
-                           float* dbs2, float* Sg, float* Sgx, const Bn2Bwd* bb, float* g_xt,
-                           const unsigned char* tmask, void* ws, size_t ws_bytes, void* stream,
-                           const float* msg = nullptr, float* dWt1f = nullptr);
-
-extern "C" int pfsgnn_source_bwd(int G, int NF, int NC, int F, const float* y, const float* sc,
-                                 const float* sh, const float* Qt, const float* Ws1,
-                                 const float* Ws2, const float* bs2, const float* mean,
-                                 const float* coef, const float* Rs, const float* Wt1,
-                                 const float* g_hsum, const float* g_next, const float* mu1,
-                                 const float* inv1, float* g_tot, float* GzS, float* dWs1,
-                                 float* dWs2, float* dbs2, float* Sg, float* Sgx, float* g_xt,
-                                 const unsigned char* tmask, void* ws, size_t ws_bytes,
-                                 void* stream) {
-  return source_bwd_impl(nullptr, G, NF, NC, F, y, sc, sh, Qt, Ws1, Ws2, bs2, mean, coef, Rs, Wt1,
-                         g_hsum, g_next, mu1, inv1, g_tot, GzS, dWs1, dWs2, dbs2, Sg, Sgx, nullptr,
-                         g_xt, tmask, ws, ws_bytes, stream);
-}
-
-extern "C" int pfsgnn_source_bwd_bn(int G, int NF, int NC, int F, const float* y, const float* sc,
-                                    const float* sh, const float* Qt, const float* Ws1,
-                                    const float* Ws2, const float* bs2, const float* mean,
-                                    const float* coef, const float* Rs, const float* Wt1,
-                                    const float* g_hsum, const float* g_next, const float* mu1,
-                                    const float* inv1, const float* var1, const float* gamma,
-                                    long long n, float eps, float* g_tot, float* GzS, float* dWs1,
-                                    float* dWs2, float* dbs2, float* alpha, float* gam0,
-                                    float* gam1, float* dgamma, float* dbeta, float* g_xt,
-                                    const unsigned char* tmask, void* ws, size_t ws_bytes,
-                                    void* stream) {
-  PF_REQUIRE(mu1 && inv1 && var1 && gamma && n > 0 && alpha && gam0 && gam1 && dgamma && dbeta,
-             "pfsgnn_source_bwd_bn", "null");
-  const Bn2Bwd bb{gamma, mu1, var1, n, eps, alpha, gam0, gam1, dgamma, dbeta};
-  return source_bwd_impl(nullptr, G, NF, NC, F, y, sc, sh, Qt, Ws1, Ws2, bs2, mean, coef, Rs, Wt1,
-                         g_hsum, g_next, mu1, inv1, g_tot, GzS, dWs1, dWs2, dbs2, nullptr, nullptr,
-                         &bb, g_xt, tmask, ws, ws_bytes, stream);
-}
-
-extern "C" int pfsgnn_source_bwd_msg(int G, int NF, int NC, int F, const float* y,
-                                     const float* sc, const float* sh, const float* Qt,
-                                     const float* Ws1, const float* Ws2, const float* bs2,
-                                     const float* mean, const float* coef, const float* Rs,
-                                     const float* Wt1, const float* g_hsum, const float* g_next,
-                                     const float* mu1, const float* inv1, float* g_tot, float* GzS,
-                                     float* dWs1, float* dWs2, float* dbs2, float* Sg, float* Sgx,
-                                     float* g_xt, const unsigned char* tmask, const float* msg,
-                                     void* ws, size_t ws_bytes, void* stream) {
-  PF_REQUIRE(msg, "pfsgnn_source_bwd_msg", "null message cache");
-  return source_bwd_impl(nullptr, G, NF, NC, F, y, sc, sh, Qt, Ws1, Ws2, bs2, mean, coef, Rs, Wt1,
-                         g_hsum, g_next, mu1, inv1, g_tot, GzS, dWs1, dWs2, dbs2, Sg, Sgx, nullptr,
-                         g_xt, tmask, ws, ws_bytes, stream, msg);
-}
-
-extern "C" int pfsgnn_source_bwd_bn_msg(
-    int G, int NF, int NC, int F, const float* y, const float* sc, const float* sh,
-    const float* Qt, const float* Ws1, const float* Ws2, const float* bs2, const float* mean,
-    const float* coef, const float* Rs, const float* Wt1, const float* g_hsum,
-    const float* g_next, const float* mu1, const float* inv1, const float* var1,
-    const float* gamma, long long n, float eps, float* g_tot, float* GzS, float* dWs1,
-    float* dWs2, float* dbs2, float* alpha, float* gam0, float* gam1, float* dgamma,
-    float* dbeta, float* g_xt, const unsigned char* tmask, const float* msg, void* ws,
-    size_t ws_bytes, void* stream) {
-  PF_REQUIRE(msg && mu1 && inv1 && var1 && gamma && n > 0 && alpha && gam0 && gam1 && dgamma &&
-                 dbeta,
-             "pfsgnn_source_bwd_bn_msg", "null");
-  const Bn2Bwd bb{gamma, mu1, var1, n, eps, alpha, gam0, gam1, dgamma, dbeta};
-  return source_bwd_impl(nullptr, G, NF, NC, F, y, sc, sh, Qt, Ws1, Ws2, bs2, mean, coef, Rs, Wt1,
-                         g_hsum, g_next, mu1, inv1, g_tot, GzS, dWs1, dWs2, dbs2, nullptr, nullptr,
-                         &bb, g_xt, tmask, ws, ws_bytes, stream, msg);
-}
-
-extern "C" int pfsgnn_source_bwd_fold(
-    int G, int NF, int NC, int F, const float* y, const float* sc, const float* sh,
-    const float* Qt, const float* Ws1, const float* Ws2, const float* bs2, const float* mean,
-    const float* coef, const float* Rs, const float* Wt1, const float* g_hsum,
-    const float* g_next, const float* mu1, const float* inv1, const float* var1,
-    const float* gamma, long long n, float eps, float* g_tot, float* GzS, float* dWs1,
-    float* dWs2, float* dbs2, float* Sg, float* Sgx, float* alpha, float* gam0, float* gam1,
-    float* dgamma, float* dbeta, float* g_xt, const unsigned char* tmask, const float* msg,
-    float* dWt1, void* ws, size_t ws_bytes, void* stream) {
-  const char* where = "pfsgnn_source_bwd_fold";
-  PF_REQUIRE(dWt1 && tmask && Rs, where, "the folded pair needs dWt1, tmask and TModel's part");
-  if (!gamma)   // the BatchNorm sums only (pfsgnn_source_bwd / _msg)
-    return source_bwd_impl(nullptr, G, NF, NC, F, y, sc, sh, Qt, Ws1, Ws2, bs2, mean, coef, Rs,
-                           Wt1, g_hsum, g_next, mu1, inv1, g_tot, GzS, dWs1, dWs2, dbs2, Sg, Sgx,
-                           nullptr, g_xt, tmask, ws, ws_bytes, stream, msg, dWt1);
-  PF_REQUIRE(mu1 && inv1 && var1 && n > 0 && alpha && gam0 && gam1 && dgamma && dbeta, where,
-             "null");
-  const Bn2Bwd bb{gamma, mu1, var1, n, eps, alpha, gam0, gam1, dgamma, dbeta};
-  return source_bwd_impl(nullptr, G, NF, NC, F, y, sc, sh, Qt, Ws1, Ws2, bs2, mean, coef, Rs, Wt1,
-                         g_hsum, g_next, mu1, inv1, g_tot, GzS, dWs1, dWs2, dbs2, nullptr, nullptr,
-                         &bb, g_xt, tmask, ws, ws_bytes, stream, msg, dWt1);
-}
-
-extern "C" int pfsgnn_sl_source_bwd(const pfsgnn_sliced_t* sl, int G, int NF, int NC, int F,
-                                    const float* y, const float* sc, const float* sh,
-                                    const float* Qt, const float* Ws1, const float* Ws2,
-                                    const float* bs2, const float* mean, const float* coef,
-                                    const float* Rs, const float* Wt1, const float* g_hsum,
-                                    const float* g_next, const float* mu1, const float* inv1,
-                                    float* g_tot, float* GzS, float* dWs1, float* dWs2,
-                                    float* dbs2, float* Sg, float* Sgx, float* g_xt,
-                                    const unsigned char* tmask, void* ws, size_t ws_bytes,
-                                    void* stream) {
-  PF_REQUIRE(sl, "pfsgnn_sl_source_bwd", "null layout");
-  return source_bwd_impl(sl, G, NF, NC, F, y, sc, sh, Qt, Ws1, Ws2, bs2, mean, coef, Rs, Wt1,
-                         g_hsum, g_next, mu1, inv1, g_tot, GzS, dWs1, dWs2, dbs2, Sg, Sgx, nullptr,
-                         g_xt, tmask, ws, ws_bytes, stream);
-}
-
-extern "C" int pfsgnn_sl_source_bwd_bn(
-    const pfsgnn_sliced_t* sl, int G, int NF, int NC, int F, const float* y, const float* sc,
-    const float* sh, const float* Qt, const float* Ws1, const float* Ws2, const float* bs2,
-    const float* mean, const float* coef, const float* Rs, const float* Wt1, const float* g_hsum,
-    const float* g_next, const float* mu1, const float* inv1, const float* var1,
-    const float* gamma, long long n, float eps, float* g_tot, float* GzS, float* dWs1,
-    float* dWs2, float* dbs2, float* alpha, float* gam0, float* gam1, float* dgamma, float* dbeta,
-    float* g_xt, const unsigned char* tmask, void* ws, size_t ws_bytes, void* stream) {
-  PF_REQUIRE(sl && mu1 && inv1 && var1 && gamma && n > 0 && alpha && gam0 && gam1 && dgamma &&
-                 dbeta,
-             "pfsgnn_sl_source_bwd_bn", "null");
-  const Bn2Bwd bb{gamma, mu1, var1, n, eps, alpha, gam0, gam1, dgamma, dbeta};
-  return source_bwd_impl(sl, G, NF, NC, F, y, sc, sh, Qt, Ws1, Ws2, bs2, mean, coef, Rs, Wt1,
-                         g_hsum, g_next, mu1, inv1, g_tot, GzS, dWs1, dWs2, dbs2, nullptr, nullptr,
-                         &bb, g_xt, tmask, ws, ws_bytes, stream);
-}
-
-static int source_bwd_impl(const pfsgnn_sliced_t* sl, int G, int NF, int NC, int F,
-                           const float* y, const float* sc, const float* sh, const float* Qt,
-                           const float* Ws1, const float* Ws2, const float* bs2, const float* mean,
-                           const float* coef, const float* Rs, const float* Wt1,
-                           const float* g_hsum, const float* g_next, const float* mu1,
-                           const float* inv1, float* g_tot, float* GzS, float* dWs1, float* dWs2,
-                           float* dbs2, float* Sg, float* Sgx, const Bn2Bwd* bb, float* g_xt,
-                           const unsigned char* tmask, void* ws, size_t ws_bytes, void* stream,
-                           const float* msg, float* dWt1f) {
+static int source_bwd_impl(const pfsgnn_source_bwd_args& a, void* ws, size_t ws_bytes,
+                           void* stream) {
+  const int G = a.G, NF = a.NF, NC = a.NC, F = a.F;
+  const pfsgnn_sliced_t* sl = a.sl;
   if (int rc = check_dims("pfsgnn_source_bwd", G, NF, NC, F)) return rc;
-  PF_REQUIRE(!msg || (!sl && msg_bytes(G, NF, NC, F) > 0), "pfsgnn_source_bwd_msg",
-             "the message cache is not kept on this path (pfsgnn_msg_bytes is 0)");
-  if (int rc = check_sliced("pfsgnn_source_bwd", sl, NC, F)) return rc;
-  PF_REQUIRE(y && Qt && Ws1 && Ws2 && bs2 && mean && coef && g_tot && GzS && dWs1 && dWs2 && dbs2,
+  PF_REQUIRE(!(sl && a.msg), "pfsgnn_source_bwd", "sl with msg: no message cache on a sliced batch");
+  PF_REQUIRE(!(sl && a.dWt1), "pfsgnn_source_bwd", "sl with dWt1: no folded pair on a sliced batch");
+  PF_REQUIRE(!a.msg || msg_bytes(G, NF, NC, F) > 0, "pfsgnn_source_bwd",
+             "msg: the message cache is not kept on this path (pfsgnn_msg_bytes is 0)");
+  PF_REQUIRE(a.y && a.Qt && a.Ws1 && a.Ws2 && a.bs2 && a.mean && a.coef && a.g_tot && a.GzS &&
+                 a.dWs1 && a.dWs2 && a.dbs2,
              "pfsgnn_source_bwd", "null");
-  PF_REQUIRE((Rs == nullptr) == (Wt1 == nullptr) && (Rs == nullptr) == (g_hsum == nullptr),
+  PF_REQUIRE((a.Rs == nullptr) == (a.Wt1 == nullptr) && (a.Rs == nullptr) == (a.g_hsum == nullptr),
              "pfsgnn_source_bwd", "Rs, Wt1, g_hsum must be given together");
-  PF_REQUIRE(!mu1 || (inv1 && ((Sg && Sgx) || bb)), "pfsgnn_source_bwd",
+  PF_REQUIRE(!a.dWt1 || (a.tmask && a.Rs), "pfsgnn_source_bwd",
+             "dWt1: the folded pair needs tmask and TModel's part (Rs, Wt1, g_hsum)");
+  PF_REQUIRE(!a.gamma || (a.mu1 && a.inv1 && a.var1 && a.n > 0 && a.alpha && a.gam0 && a.gam1 &&
+                          a.dgamma && a.dbeta),
+             "pfsgnn_source_bwd",
+             "gamma needs mu1, inv1, var1, n, alpha, gam0, gam1, dgamma, dbeta");
+  PF_REQUIRE(!a.mu1 || (a.inv1 && ((a.Sg && a.Sgx) || a.gamma)), "pfsgnn_source_bwd",
              "mu1 needs inv1, Sg, Sgx");
+  if (int rc = check_sliced("pfsgnn_source_bwd", sl, NC, F)) return rc;
+  // gamma: the BatchNorm coefficients in place of its two sums (Sg / Sgx unused)
+  const Bn2Bwd bbv{a.gamma, a.mu1, a.var1, a.n, a.eps, a.alpha, a.gam0, a.gam1, a.dgamma, a.dbeta};
+  const Bn2Bwd* bb = a.gamma ? &bbv : nullptr;
+  float *Sg = bb ? nullptr : a.Sg, *Sgx = bb ? nullptr : a.Sgx;
   const EdgeGeo geo = geo_of(G, NF, NC, sl);
   const int C = 2 * F;
   const size_t nb = geo.nblocks;
   Ws w{reinterpret_cast<char*>(ws), ws_bytes};
-  // (dWt1f: TModel's edge weight gradient dWt1[:, F:2F] from this kernel too,
-  // the other half of pfsgnn_target_bwd_fold's mask-only form)
-  const bool fold = dWt1f && tmask && Rs && !sl && tbwd_folds(F);
+  // (dWt1: TModel's edge weight gradient dWt1[:, F:2F] from this kernel too,
+  // the other half of target_bwd's mask-only form)
+  const bool fold = a.dWt1 && tbwd_folds(F);
   const size_t nW = nb * C * (C + 1) + nb * C * F * (fold ? 2 : 1);
   float* pW2 = pf::defer_take(nW);
   const bool defer = pW2 != nullptr;
@@ -2304,41 +2087,42 @@ static int source_bwd_impl(const pfsgnn_sliced_t* sl, int G, int NF, int NC, int
   float* pBN = w.take(nb * 2 * F);
   hipStream_t st = as_stream(stream);
   const bool mfma = sl || use_mfma();
-  const float* QtT = mfma ? Qt : class_rows(Qt, C, geo, w, st);
-  const float* ghT = mfma ? g_hsum : class_rows(g_hsum, C, geo, w, st);
-  PF_REQUIRE(pW2 && pW1 && pCol && pBN && QtT && (ghT || !g_hsum), "pfsgnn_source_bwd",
+  const float* QtT = mfma ? a.Qt : class_rows(a.Qt, C, geo, w, st);
+  const float* ghT = mfma ? a.g_hsum : class_rows(a.g_hsum, C, geo, w, st);
+  PF_REQUIRE(pW2 && pW1 && pCol && pBN && QtT && (ghT || !a.g_hsum), "pfsgnn_source_bwd",
              "workspace too small");
   { pf::Timer tm_("source_bwd", st);
   if (sl) {
     float* tabs = w.take((size_t)pfm::sl_tab_floats(geo, F));
     PF_REQUIRE(tabs, "pfsgnn_source_bwd", "workspace too small");
-    if (int rc = pfm::sl_source_bwd(geo, sl_of(*sl), F, y, sc, sh, QtT, Ws1, Ws2, bs2, mean, coef,
-                                    Rs, Wt1, ghT, g_next, mu1, inv1, g_tot, pW2, pW1, pCol, pBN,
-                                    tmask, tabs, mf_prec(1, F), st))
+    if (int rc = pfm::sl_source_bwd(geo, sl_of(*sl), F, a.y, a.sc, a.sh, QtT, a.Ws1, a.Ws2, a.bs2,
+                                    a.mean, a.coef, a.Rs, a.Wt1, ghT, a.g_next, a.mu1, a.inv1,
+                                    a.g_tot, pW2, pW1, pCol, pBN, a.tmask, tabs, mf_prec(1, F), st))
       return rc;
   } else if (mfma) {
     for (int rep = 0, nrep = 1 + pf::repeats("source_bwd"); rep < nrep; ++rep)
-      if (int rc = pfm::source_bwd(geo, F, msg, y, sc, sh, QtT, Ws1, Ws2, bs2, mean, coef, Rs, Wt1,
-                                   ghT, g_next, mu1, inv1, g_tot, pW2, pW1, pCol, pBN, tmask,
-                                   mf_prec(1, F), st, pWt))
+      if (int rc = pfm::source_bwd(geo, F, a.msg, a.y, a.sc, a.sh, QtT, a.Ws1, a.Ws2, a.bs2, a.mean,
+                                   a.coef, a.Rs, a.Wt1, ghT, a.g_next, a.mu1, a.inv1, a.g_tot, pW2,
+                                   pW1, pCol, pBN, a.tmask, mf_prec(1, F), st, pWt))
         return rc;
   } else {
-  DISPATCH_F(F, hipLaunchKernelGGL(k_source_bwd<FF>, dim3(edge_grid(geo)), dim3(256), 0, st, geo, y,
-                                   sc, sh, QtT, Ws1, Ws2, bs2, mean, coef, Rs, Wt1, ghT, g_next,
-                                   mu1, inv1, g_tot, pW2, pW1, pCol, pBN));
+  DISPATCH_F(F, hipLaunchKernelGGL(k_source_bwd<FF>, dim3(edge_grid(geo)), dim3(256), 0, st, geo,
+                                   a.y, a.sc, a.sh, QtT, a.Ws1, a.Ws2, a.bs2, a.mean, a.coef, a.Rs,
+                                   a.Wt1, ghT, a.g_next, a.mu1, a.inv1, a.g_tot, pW2, pW1, pCol,
+                                   pBN));
   }
   tm_.end(); }
   {
     RedDesc rd[6] = {{pBN, (int)nb, (size_t)2 * F, F, 1, F, Sg, F, 0, 1.f},
                      {pBN + F, (int)nb, (size_t)2 * F, F, 1, F, Sgx, F, 0, 1.f},
-                     {pW2, (int)nb, (size_t)C * (C + 1), C + 1, C, C, dWs2, C, 1, 1.f},
-                     {pW2 + C, (int)nb, (size_t)C * (C + 1), C + 1, C, 1, dbs2, 1, 1, 1.f},
-                     {pW1, (int)nb, (size_t)C * F, F, C, F, dWs1 + F, C, 1, 1.f},
-                     {pWt, (int)nb, (size_t)C * F, F, C, F, fold ? dWt1f + F : nullptr, C, 1, 1.f}};
+                     {pW2, (int)nb, (size_t)C * (C + 1), C + 1, C, C, a.dWs2, C, 1, 1.f},
+                     {pW2 + C, (int)nb, (size_t)C * (C + 1), C + 1, C, 1, a.dbs2, 1, 1, 1.f},
+                     {pW1, (int)nb, (size_t)C * F, F, C, F, a.dWs1 + F, C, 1, 1.f},
+                     {pWt, (int)nb, (size_t)C * F, F, C, F, fold ? a.dWt1 + F : nullptr, C, 1, 1.f}};
     const int nw = fold ? 4 : 3;   // weight-gradient reductions
     // the BatchNorm sums are read at once (bn2_bwd_coef); the weight
     // gradients only by the optimizer
-    const bool sums = mu1 && !bb;   // BN sums by the generic reduce
+    const bool sums = a.mu1 && !bb;   // BN sums by the generic reduce
     const RedDesc* now = sums ? rd : rd + 2;
     int nnow = (sums ? 2 : 0) + nw;
     if (defer) {
@@ -2349,9 +2133,9 @@ static int source_bwd_impl(const pfsgnn_sliced_t* sl, int G, int NF, int NC, int
   }
   // g_xt += Ws1[:, 0:F]^T GzS (gnn.py:136, the x_t[tgt] input gradient), with
   // the BatchNorm backward coefficients in the same launch when both are due
-  const NodeLin Lx = lin_t_add(g_xt ? Ws1 : nullptr, 2 * F, 0, F, g_xt, geo.NT);
+  const NodeLin Lx = lin_t_add(a.g_xt ? a.Ws1 : nullptr, 2 * F, 0, F, a.g_xt, geo.NT);
   if (bb && Lx.W) {
-    const ColRed cr{pCol, G, col_bpg(geo, sl), NC, GzS, Lx, no_lin()};
+    const ColRed cr{pCol, G, col_bpg(geo, sl), NC, a.GzS, Lx, no_lin()};
     const int nbc = (int)(((long long)G * NC + 3) / 4);
     DISPATCH_C(C, hipLaunchKernelGGL(k_bn2_coef_columns_lin<CC>, dim3(F + nbc), dim3(256), 0, st,
                                      pBN, (int)nb, F, *bb, Sg, Sgx, cr));
@@ -2359,9 +2143,15 @@ static int source_bwd_impl(const pfsgnn_sliced_t* sl, int G, int NF, int NC, int
     if (bb)
       hipLaunchKernelGGL(k_bn2_coef_part, dim3(F), dim3(256), 0, st, pBN, (int)nb, F, *bb, Sg,
                          Sgx);
-    if (int rc = columns_lin(pCol, G, col_bpg(geo, sl), NC, C, GzS, Lx, no_lin(), st)) return rc;
+    if (int rc = columns_lin(pCol, G, col_bpg(geo, sl), NC, C, a.GzS, Lx, no_lin(), st)) return rc;
   }
   return pf::check_launch("pfsgnn_source_bwd");
+}
+
+extern "C" int pfsgnn_source_bwd(const pfsgnn_source_bwd_args* a, void* ws, size_t ws_bytes,
+                                 void* stream) {
+  PF_REQUIRE(a, "pfsgnn_source_bwd", "null arguments");
+  return pf::take_pending(source_bwd_impl(*a, ws, ws_bytes, stream));
 }
 
 extern "C" int pfsgnn_edge_bn_grad_sums(int G, int NF, int NC, int F, const float* g,
@@ -2387,18 +2177,15 @@ extern "C" int pfsgnn_edge_bn_grad_sums(int G, int NF, int NC, int F, const floa
   return pf::check_launch("pfsgnn_edge_bn_grad_sums");
 }
 
-static int edge_mlp_bwd_impl(const pfsgnn_sliced_t* sl, int G, int NF, int NC, int F,
-                             const float* g_tot, const float* alpha, const float* gam0,
-                             const float* gam1, const float* y, const float* xe, const float* xsc,
-                             const float* xsh, const float* Ps, const float* Pt, const float* W1,
-                             const float* W2, float* dW1, float* dW2, float* db2, float* gxe,
-                             float* GzEs, float* GzEt, float* g_xs, float* g_xt, float* Vu,
-                             void* ws, size_t ws_bytes, void* stream) {
+static int edge_mlp_bwd_impl(const pfsgnn_edge_mlp_bwd_args& a, void* ws, size_t ws_bytes,
+                             void* stream) {
+  const int G = a.G, NF = a.NF, NC = a.NC, F = a.F;
+  const pfsgnn_sliced_t* sl = a.sl;
   if (int rc = check_dims("pfsgnn_edge_mlp_bwd", G, NF, NC, F)) return rc;
-  if (int rc = check_sliced("pfsgnn_edge_mlp_bwd", sl, NC, F)) return rc;
-  PF_REQUIRE(g_tot && alpha && gam0 && gam1 && y && xe && Ps && Pt && W1 && W2 && dW1 && dW2 &&
-                 db2 && GzEs && GzEt,
+  PF_REQUIRE(a.g_tot && a.alpha && a.gam0 && a.gam1 && a.y && a.xe && a.Ps && a.Pt && a.W1 &&
+                 a.W2 && a.dW1 && a.dW2 && a.db2 && a.GzEs && a.GzEt,
              "pfsgnn_edge_mlp_bwd", "null");
+  if (int rc = check_sliced("pfsgnn_edge_mlp_bwd", sl, NC, F)) return rc;
   const EdgeGeo geo = geo_of(G, NF, NC, sl);
   const int H = 4 * F;
   const size_t nb = geo.nblocks;
@@ -2408,16 +2195,16 @@ static int edge_mlp_bwd_impl(const pfsgnn_sliced_t* sl, int G, int NF, int NC, i
   if (!defer) pW2 = w.take(nb * F * (H + 1) + nb * H * F);
   float* pW1 = pW2 ? pW2 + nb * F * (H + 1) : nullptr;
   float* pCol = w.take((size_t)G * col_bpg(geo, sl) * NC * H);
-  float* gs = fiber_dst(geo, H, GzEs, w);
+  float* gs = fiber_dst(geo, H, a.GzEs, w);
   hipStream_t st = as_stream(stream);
   if (sl) {
     PF_REQUIRE(pW2 && pW1 && pCol && gs, "pfsgnn_edge_mlp_bwd", "workspace too small");
     pf::Timer tm_("edge_mlp_bwd", st);
     float* tabs = w.take((size_t)pfm::sl_tab_floats(geo, F));
     PF_REQUIRE(tabs, "pfsgnn_edge_mlp_bwd", "workspace too small");
-    if (int rc = pfm::sl_edge_mlp_bwd(geo, sl_of(*sl), F, g_tot, alpha, gam0, gam1, y, xe, xsc,
-                                      xsh, Ps, Pt, W1, W2, gxe, gs, pW2, pW1, pCol, tabs,
-                                      mf_prec(0, F), st))
+    if (int rc = pfm::sl_edge_mlp_bwd(geo, sl_of(*sl), F, a.g_tot, a.alpha, a.gam0, a.gam1, a.y,
+                                      a.xe, a.xsc, a.xsh, a.Ps, a.Pt, a.W1, a.W2, a.gxe, gs, pW2,
+                                      pW1, pCol, tabs, mf_prec(0, F), st))
       return rc;
     tm_.end();
   } else if (use_mfma()) {
@@ -2427,63 +2214,44 @@ static int edge_mlp_bwd_impl(const pfsgnn_sliced_t* sl, int G, int NF, int NC, i
     // overwrites its outputs -- whose marginal cost in a replayed graph is the
     // kernel's in-situ duration, bench.py's roofline)
     for (int rep = 0, nrep = 1 + pf::repeats("edge_mlp_bwd"); rep < nrep; ++rep)
-      if (int rc = pfm::edge_mlp_bwd(geo, F, g_tot, alpha, gam0, gam1, y, xe, xsc, xsh, Ps, Pt,
-                                     W1, W2, gxe, gs, pW2, pW1, pCol, mf_prec(0, F), st))
+      if (int rc = pfm::edge_mlp_bwd(geo, F, a.g_tot, a.alpha, a.gam0, a.gam1, a.y, a.xe, a.xsc,
+                                     a.xsh, a.Ps, a.Pt, a.W1, a.W2, a.gxe, gs, pW2, pW1, pCol,
+                                     mf_prec(0, F), st))
         return rc;
     tm_.end();
   } else {
-  const float* PtT = class_rows(Pt, H, geo, w, st);
-  const float* W2T = transposed(W2, F, H, w, st);
+  const float* PtT = class_rows(a.Pt, H, geo, w, st);
+  const float* W2T = transposed(a.W2, F, H, w, st);
   PF_REQUIRE(pW2 && pW1 && pCol && gs && PtT && W2T, "pfsgnn_edge_mlp_bwd", "workspace too small");
   { pf::Timer tm_("edge_mlp_bwd", st);
   DISPATCH_F(F, hipLaunchKernelGGL(k_edge_mlp_bwd<FF>, dim3(edge_grid(geo)), dim3(256), 0, st, geo,
-                                   g_tot, alpha, gam0, gam1, y, xe, xsc, xsh, Ps, PtT, W1, W2T, gxe,
-                                   gs, pW2, pW1, pCol));
+                                   a.g_tot, a.alpha, a.gam0, a.gam1, a.y, a.xe, a.xsc, a.xsh, a.Ps,
+                                   PtT, a.W1, W2T, a.gxe, gs, pW2, pW1, pCol));
   tm_.end(); }
   }
   // node-input gradients of the first Linear (gnn.py:100): g_xs += W1[:, 0:F]^T GzEs,
   // g_xt += W1[:, F:2F]^T GzEt, and Vu = W1[:, 3F:4F]^T GzEt per class (the
   // caller sums it per graph into g_u)
   {
-    RedDesc rd[3] = {{pW2, (int)nb, (size_t)F * (H + 1), H + 1, F, H, dW2, H, 1, 1.f},
-                     {pW2 + H, (int)nb, (size_t)F * (H + 1), H + 1, F, 1, db2, 1, 1, 1.f},
-                     {pW1, (int)nb, (size_t)H * F, F, H, F, dW1 + 2 * F, H, 1, 1.f}};
+    RedDesc rd[3] = {{pW2, (int)nb, (size_t)F * (H + 1), H + 1, F, H, a.dW2, H, 1, 1.f},
+                     {pW2 + H, (int)nb, (size_t)F * (H + 1), H + 1, F, 1, a.db2, 1, 1, 1.f},
+                     {pW1, (int)nb, (size_t)H * F, F, H, F, a.dW1 + 2 * F, H, 1, 1.f}};
     if (defer) pf::defer_push(rd, 3);
     else launch_reduce_multi(rd, 3, st);
   }
-  NodeLin Lu = lin_t_add(Vu ? W1 : nullptr, 4 * F, 3 * F, F, Vu, geo.NT);
+  NodeLin Lu = lin_t_add(a.Vu ? a.W1 : nullptr, 4 * F, 3 * F, F, a.Vu, geo.NT);
   Lu.add = 0;
-  if (int rc = fiber_columns_lin(geo, H, gs, GzEs,
-                                 lin_t_add(g_xs ? W1 : nullptr, 4 * F, 0, F, g_xs, geo.NS),
-                                 no_lin(), pCol, col_bpg(geo, sl), GzEt,
-                                 lin_t_add(g_xt ? W1 : nullptr, 4 * F, F, F, g_xt, geo.NT), Lu, st))
+  if (int rc = fiber_columns_lin(geo, H, gs, a.GzEs,
+                                 lin_t_add(a.g_xs ? a.W1 : nullptr, 4 * F, 0, F, a.g_xs, geo.NS),
+                                 no_lin(), pCol, col_bpg(geo, sl), a.GzEt,
+                                 lin_t_add(a.g_xt ? a.W1 : nullptr, 4 * F, F, F, a.g_xt, geo.NT),
+                                 Lu, st))
     return rc;
   return pf::check_launch("pfsgnn_edge_mlp_bwd");
 }
 
-extern "C" int pfsgnn_edge_mlp_bwd(int G, int NF, int NC, int F, const float* g_tot,
-                                   const float* alpha, const float* gam0, const float* gam1,
-                                   const float* y, const float* xe, const float* xsc,
-                                   const float* xsh, const float* Ps, const float* Pt,
-                                   const float* W1, const float* W2, float* dW1, float* dW2,
-                                   float* db2, float* gxe, float* GzEs, float* GzEt,
-                                   float* g_xs, float* g_xt, float* Vu, void* ws,
-                                   size_t ws_bytes, void* stream) {
-  return edge_mlp_bwd_impl(nullptr, G, NF, NC, F, g_tot, alpha, gam0, gam1, y, xe, xsc, xsh, Ps,
-                           Pt, W1, W2, dW1, dW2, db2, gxe, GzEs, GzEt, g_xs, g_xt, Vu, ws,
-                           ws_bytes, stream);
-}
-
-extern "C" int pfsgnn_sl_edge_mlp_bwd(const pfsgnn_sliced_t* sl, int G, int NF, int NC, int F,
-                                      const float* g_tot, const float* alpha, const float* gam0,
-                                      const float* gam1, const float* y, const float* xe,
-                                      const float* xsc, const float* xsh, const float* Ps,
-                                      const float* Pt, const float* W1, const float* W2,
-                                      float* dW1, float* dW2, float* db2, float* gxe, float* GzEs,
-                                      float* GzEt, float* g_xs, float* g_xt, float* Vu, void* ws,
-                                      size_t ws_bytes, void* stream) {
-  PF_REQUIRE(sl, "pfsgnn_sl_edge_mlp_bwd", "null layout");
-  return edge_mlp_bwd_impl(sl, G, NF, NC, F, g_tot, alpha, gam0, gam1, y, xe, xsc, xsh, Ps, Pt, W1,
-                           W2, dW1, dW2, db2, gxe, GzEs, GzEt, g_xs, g_xt, Vu, ws, ws_bytes,
-                           stream);
+extern "C" int pfsgnn_edge_mlp_bwd(const pfsgnn_edge_mlp_bwd_args* a, void* ws, size_t ws_bytes,
+                                   void* stream) {
+  PF_REQUIRE(a, "pfsgnn_edge_mlp_bwd", "null arguments");
+  return pf::take_pending(edge_mlp_bwd_impl(*a, ws, ws_bytes, stream));
 }

@@ -195,7 +195,7 @@ class Engine:
 
     def _fiber_bn_sums(self, d, ss):
         """SModel's node_mlp_2 BatchNorm backward sums made by TModel's edge
-        backward, whose epilogue finishes g_xs (pfsgnn_target_bwd_bn): the
+        backward, whose epilogue finishes g_xs (pfsgnn_target_bwd's bn_part): the
         (Yp, mu, var, eps) to hand it, or None (then mlp_bwd sums them)."""
         sS = ss.get("sS")
         if (d.sp is not None or not self.normed or not getattr(self.be, "fiber_bn_sums", False)

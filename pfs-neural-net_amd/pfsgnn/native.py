@@ -138,6 +138,63 @@ class BlockTail(ctypes.Structure):
                 + _ptrs("means", "gZ", "gV", "unew", "y1", "r1", "r2",
                         "We", "be", "Ws", "bs", "Pt", "Qt"))
 
+
+# The edge ops' argument structs (include/pfsgnn.h): each begins with the batch
+# and its sliced layout (NULL: complete graphs); an optional part left out is
+# NULL / 0, which is what ctypes gives a field that is not set.
+_EDGE_HEAD = [("G", I), ("NF", I), ("NC", I), ("F", I), ("sl", SLP)]
+
+
+class EdgeMlpFwdArgs(ctypes.Structure):
+    """pfsgnn_edge_mlp_fwd_args"""
+    _fields_ = (_EDGE_HEAD
+                + _ptrs("xe", "xsc", "xsh", "Ps", "Pt", "W1", "W2", "b2", "y", "mu", "var",
+                        "gamma", "beta", "rm", "rv")
+                + [("momentum", FL), ("eps", FL)] + _ptrs("sc", "sh", "inv1", "inv2"))
+
+
+class SourceFwdArgs(ctypes.Structure):
+    """pfsgnn_source_fwd_args"""
+    _fields_ = _EDGE_HEAD + _ptrs("y", "sc", "sh", "Qt", "Ws1", "Ws2", "bs2", "mom", "hs", "msg")
+
+
+class TargetFwdArgs(ctypes.Structure):
+    """pfsgnn_target_fwd_args"""
+    _fields_ = (_EDGE_HEAD + _ptrs("y", "sc", "sh", "Rs", "Wt1", "hsum", "Wt2", "bt2")
+                + [("bscale", FL)] + _ptrs("agg", "tmask"))
+
+
+class TargetBwdArgs(ctypes.Structure):
+    """pfsgnn_target_bwd_args"""
+    _fields_ = (_EDGE_HEAD
+                + _ptrs("y", "sc", "sh", "Rs", "Wt1", "g_hsum", "GzT", "dWt1", "gxe", "g_xs",
+                        "tmask", "bn_Yp", "bn_mu", "bn_var")
+                + [("bn_eps", FL)] + _ptrs("bn_part") + [("fold", I)])
+
+
+class SourceBwdArgs(ctypes.Structure):
+    """pfsgnn_source_bwd_args"""
+    _fields_ = (_EDGE_HEAD
+                + _ptrs("y", "sc", "sh", "Qt", "Ws1", "Ws2", "bs2", "mean", "coef", "Rs", "Wt1",
+                        "g_hsum", "g_next", "mu1", "inv1", "var1", "gamma")
+                + [("n", LL), ("eps", FL)]
+                + _ptrs("g_tot", "GzS", "dWs1", "dWs2", "dbs2", "Sg", "Sgx", "alpha", "gam0",
+                        "gam1", "dgamma", "dbeta", "g_xt", "tmask", "msg", "dWt1"))
+
+
+class EdgeMlpBwdArgs(ctypes.Structure):
+    """pfsgnn_edge_mlp_bwd_args"""
+    _fields_ = (_EDGE_HEAD
+                + _ptrs("g_tot", "alpha", "gam0", "gam1", "y", "xe", "xsc", "xsh", "Ps", "Pt",
+                        "W1", "W2", "dW1", "dW2", "db2", "gxe", "GzEs", "GzEt", "g_xs", "g_xt",
+                        "Vu"))
+
+
+# op name -> argument struct, in the order of the PFSGNN_OP_* codes
+EDGE_ARGS = {"edge_mlp_fwd": EdgeMlpFwdArgs, "source_fwd": SourceFwdArgs,
+             "target_fwd": TargetFwdArgs, "target_bwd": TargetBwdArgs,
+             "source_bwd": SourceBwdArgs, "edge_mlp_bwd": EdgeMlpBwdArgs}
+
 _SIGS = {
     "pfsgnn_version": ([], ctypes.c_char_p),
     "pfsgnn_last_error": ([], ctypes.c_char_p),
@@ -212,24 +269,10 @@ _SIGS = {
     "pfsgnn_rows_stats": ([P, I, LL, P, P, P, SZ, P], I),
     "pfsgnn_rows_bn_sums": ([P, P, I, LL, P, P, P, P, P, SZ, P], I),
     "pfsgnn_rows_axpby": ([P, P, I, LL, P, P, P, P, P], I),
-    "pfsgnn_edge_mlp_fwd": ([I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, SZ, P], I),
-    "pfsgnn_edge_mlp_fwd_bn": ([I, I, I, I] + [P] * 15 + [FL, FL, P, P, P, P, P, SZ, P], I),
-    "pfsgnn_source_fwd": ([I, I, I, I, P, P, P, P, P, P, P, P, P, P, SZ, P], I),
-    "pfsgnn_target_fwd": ([I, I, I, I, P, P, P, P, P, P, P, P, FL, P, P, P, SZ, P], I),
     "pfsgnn_tmask_bytes": ([I, I, I, I], SZ),
-    "pfsgnn_target_bwd": ([I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, SZ, P], I),
-    "pfsgnn_target_bwd_bn": ([I, I, I, I] + [P] * 14 + [FL, P, P, SZ, P], I),
     "pfsgnn_tbwd_fold": ([I], I),
-    "pfsgnn_target_bwd_fold": ([I, I, I, I] + [P] * 14 + [FL, P, P, SZ, P], I),
-    "pfsgnn_source_bwd_fold": ([I, I, I, I] + [P] * 17 + [LL, FL] + [P] * 16 + [P, SZ, P], I),
-    "pfsgnn_source_bwd": ([I, I, I, I] + [P] * 24 + [P, SZ, P], I),
-    "pfsgnn_source_bwd_bn": ([I, I, I, I] + [P] * 17 + [LL, FL] + [P] * 12 + [P, SZ, P], I),
     "pfsgnn_msg_bytes": ([I, I, I, I], SZ),
-    "pfsgnn_source_fwd_msg": ([I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, SZ, P], I),
-    "pfsgnn_source_bwd_msg": ([I, I, I, I] + [P] * 25 + [P, SZ, P], I),
-    "pfsgnn_source_bwd_bn_msg": ([I, I, I, I] + [P] * 17 + [LL, FL] + [P] * 13 + [P, SZ, P], I),
     "pfsgnn_edge_bn_grad_sums": ([I, I, I, I, P, P, P, P, P, P, P, SZ, P], I),
-    "pfsgnn_edge_mlp_bwd": ([I, I, I, I] + [P] * 21 + [P, SZ, P], I),
     "pfsgnn_loss_fwd": ([I, I, I, I, P, P, P, P, P, P, P, P, FL, FL, FL, ULL, P, P, P, P, P, P, P, SZ, P], I),
     "pfsgnn_loss_finalize": ([I, I, I, P, P, P, P, FL, FL, FL, FL, FL, FL, P, P, P, P, P, P, P], I),
     "pfsgnn_loss_bwd": ([I, I, I, I, P, P, P, P, P, P, P, P, FL, FL, FL, ULL, P, P, P, P, P, P,
@@ -256,18 +299,21 @@ _SIGS = {
     "pfsgnn_edges_to_slots": ([P, LL, LL, I, P, P, P], I),
     "pfsgnn_edges_from_slots": ([P, P, P, LL, LL, I, P, I, P, P], I),
     "pfsgnn_sl_tmask_bytes": ([SLP, I], SZ),
+    "pfsgnn_edge_args_bytes": ([I], SZ),
 }
-# the edge ops on a sliced general batch: the complete op's arguments after the layout
-for _op in ("edge_mlp_fwd", "edge_mlp_fwd_bn", "source_fwd", "target_fwd", "target_bwd",
-            "source_bwd", "source_bwd_bn", "edge_mlp_bwd"):
-    _SIGS["pfsgnn_sl_" + _op] = ([SLP] + _SIGS["pfsgnn_" + _op][0], I)
+for _op, _cls in EDGE_ARGS.items():
+    _SIGS["pfsgnn_" + _op] = ([ctypes.POINTER(_cls), P, SZ, P], I)
 # the objective on a sliced general batch: the layout and pos_user, then the dense op's arguments
 for _op in ("loss_fwd", "loss_finalize", "loss_bwd"):
     _SIGS["pfsgnn_sl_" + _op] = ([SLP, P] + _SIGS["pfsgnn_" + _op][0], I)
 
 
+ABI_VERSION = "pfsgnn 0.2 gfx950"   # pfsgnn_version() of the library these signatures describe
+
+
 def lib():
-    """Load libpfsgnn.so (once).  Raises NativeUnavailable if it is missing."""
+    """Load libpfsgnn.so (once).  Raises NativeUnavailable if it is missing or
+    was built from sources with another C ABI."""
     global _lib
     if _lib is None:
         if not os.path.exists(_LIB_PATH):
@@ -275,6 +321,14 @@ def lib():
                 f"{_LIB_PATH} not found: build it with `make -C pfs-neural-net_amd` "
                 "(or __graft_entry__.build()); there is no non-HIP fallback")
         L = ctypes.CDLL(_LIB_PATH)
+        # a library built from other sources (a test-side or variant build left
+        # over from an earlier tree) may export the same names with other
+        # signatures: refuse it by its version rather than call into it
+        L.pfsgnn_version.restype = ctypes.c_char_p
+        if L.pfsgnn_version().decode() != ABI_VERSION:
+            raise NativeUnavailable(
+                f"{_LIB_PATH} is {L.pfsgnn_version().decode()!r}, this binding is for "
+                f"{ABI_VERSION!r}: rebuild it with `make -C pfs-neural-net_amd`")
         for name, (args, ret) in _SIGS.items():
             fn = getattr(L, name)
             fn.argtypes = args
@@ -1102,15 +1156,16 @@ class HipBackend:
         """A general batch without a sliced layout: the composed ops (pfsgnn.sparse)."""
         return d.sp is not None and d.sp.sl is None
 
-    @staticmethod
-    def _ecall(op, d, *args):
-        """Edge op `op` of the C ABI: pfsgnn_<op> on complete graphs,
-        pfsgnn_sl_<op> (same arguments after the layout) on a sliced batch."""
-        sl = d.sp.sl if d.sp is not None else None
-        if sl is None:
-            _call("pfsgnn_" + op, *args)
-        else:
-            _call("pfsgnn_sl_" + op, sl.ref, *args)
+    def _ecall(self, op, d, **fields):
+        """Edge op `op` of the C ABI: pfsgnn_<op>(its argument struct, workspace,
+        stream).  ``fields``: the struct's tensors (None: NULL) and scalars after
+        the head, which is the batch ``d`` and its sliced layout."""
+        a = EDGE_ARGS[op](G=d.G, NF=d.NF, NC=d.NC, F=d.F,
+                          sl=d.sp.sl.ref if d.sp is not None else None)
+        for k, v in fields.items():
+            setattr(a, k, v.data_ptr() if isinstance(v, torch.Tensor) else v)
+        ws, wsb = self._wsargs(d)
+        _call("pfsgnn_" + op, ctypes.byref(a), ws, wsb, _stream())
 
     def edge_mlp_fwd(self, d, xe, xsc, xsh, Ps, Pt, W1, W2, b2):
         if self._composed(d):
@@ -1118,10 +1173,8 @@ class HipBackend:
         self._set_dims(d)
         y, mu, var = self.empty(d.F, d.EP), self.empty(d.F), self.empty(d.F)
         self._chk(xe, Ps, Pt, W1, W2, b2)
-        ws, wsb = self._wsargs(d)
-        self._ecall("edge_mlp_fwd", d, d.G, d.NF, d.NC, d.F, xe.data_ptr(), _ptr(xsc), _ptr(xsh),
-              Ps.data_ptr(), Pt.data_ptr(), W1.data_ptr(), W2.data_ptr(), b2.data_ptr(),
-              y.data_ptr(), mu.data_ptr(), var.data_ptr(), ws, wsb, _stream())
+        self._ecall("edge_mlp_fwd", d, xe=xe, xsc=xsc, xsh=xsh, Ps=Ps, Pt=Pt, W1=W1, W2=W2, b2=b2,
+                    y=y, mu=mu, var=var)
         return y, mu, var
 
     def edge_mlp_fwd_bn(self, d, xe, xsc, xsh, Ps, Pt, W1, W2, b2, bn):
@@ -1137,28 +1190,20 @@ class HipBackend:
         y, mu, var = self.empty(F, d.EP), self.empty(F), self.empty(F)
         sc, sh, inv1, inv2 = self.empty(F), self.empty(F), self.empty(F), self.empty(F)
         self._chk(xe, Ps, Pt, W1, W2, b2, gamma, beta, rm, rv)
-        ws, wsb = self._wsargs(d)
-        self._ecall("edge_mlp_fwd_bn", d, d.G, d.NF, d.NC, F, xe.data_ptr(), _ptr(xsc), _ptr(xsh),
-              Ps.data_ptr(), Pt.data_ptr(), W1.data_ptr(), W2.data_ptr(), b2.data_ptr(),
-              y.data_ptr(), mu.data_ptr(), var.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
-              _ptr(rm), _ptr(rv), float(momentum), float(eps), sc.data_ptr(), sh.data_ptr(),
-              inv1.data_ptr(), inv2.data_ptr(), ws, wsb, _stream())
+        self._ecall("edge_mlp_fwd", d, xe=xe, xsc=xsc, xsh=xsh, Ps=Ps, Pt=Pt, W1=W1, W2=W2, b2=b2,
+                    y=y, mu=mu, var=var, gamma=gamma, beta=beta, rm=rm, rv=rv,
+                    momentum=float(momentum), eps=float(eps), sc=sc, sh=sh, inv1=inv1, inv2=inv2)
         return y, mu, var, sc, sh, inv1
 
     def source_fwd(self, d, y, sc, sh, Qt, Ws1, Ws2, bs2, hs_out, msg=None):
         """-> mom; ``msg`` (from ``msg_cache(d)``) receives the per-edge messages
-        for source_bwd (pfsgnn_source_fwd_msg)."""
+        for source_bwd."""
         if self._composed(d):
             return self._sp.source_fwd(d, y, sc, sh, Qt, Ws1, Ws2, bs2, hs_out)
         mom = self.empty(4, 2 * d.F, d.NS)
         self._chk(y, Qt, Ws1, Ws2, bs2, hs_out)
-        ws, wsb = self._wsargs(d)
-        args = (d.G, d.NF, d.NC, d.F, y.data_ptr(), _ptr(sc), _ptr(sh), Qt.data_ptr(),
-                Ws1.data_ptr(), Ws2.data_ptr(), bs2.data_ptr(), mom.data_ptr(), hs_out.data_ptr())
-        if msg is not None:
-            _call("pfsgnn_source_fwd_msg", *args, msg.data_ptr(), ws, wsb, _stream())
-        else:
-            self._ecall("source_fwd", d, *args, ws, wsb, _stream())
+        self._ecall("source_fwd", d, y=y, sc=sc, sh=sh, Qt=Qt, Ws1=Ws1, Ws2=Ws2, bs2=bs2, mom=mom,
+                    hs=hs_out, msg=msg)
         return mom
 
     def msg_cache(self, d):
@@ -1198,10 +1243,8 @@ class HipBackend:
             self._chk(Wt2, bt2)
             assert Wt2.shape == (2 * d.F, 2 * d.F)
             A = self.empty(2 * d.F, d.NT)
-        ws, wsb = self._wsargs(d)
-        self._ecall("target_fwd", d, d.G, d.NF, d.NC, d.F, y.data_ptr(), _ptr(sc), _ptr(sh),
-              Rs.data_ptr(), Wt1.data_ptr(), hsum.data_ptr(), _ptr(Wt2), _ptr(bt2),
-              float(bscale), _ptr(A), _ptr(tmask), ws, wsb, _stream())
+        self._ecall("target_fwd", d, y=y, sc=sc, sh=sh, Rs=Rs, Wt1=Wt1, hsum=hsum, Wt2=Wt2, bt2=bt2,
+                    bscale=float(bscale), agg=A, tmask=tmask)
         return hsum if agg is None else (hsum, A)
 
     def tbwd_fold(self, d):
@@ -1217,42 +1260,14 @@ class HipBackend:
         finished g_xs next (SModel's, gnn.py:154; complete graphs): its sums come
         out of the same call -> (GzT, gxe, partials for mlp_bwd's bn_part).
         ``fold`` (tbwd_fold(d), with ``tmask`` and no gxe): the mask-only form
-        (pfsgnn_target_bwd_fold); dWt1[:, F:2F] is then left to the source_bwd
+        (the struct's ``fold``); dWt1[:, F:2F] is then left to the source_bwd
         call that follows, which must be given ``dWt1``."""
         if fold:
-            # (where tbwd_fold(d) is false the entry point runs today's form)
+            # (where tbwd_fold(d) is false the entry point runs the unfolded form)
             assert tmask is not None and not want_gxe and d.sp is None
-            self._chk(g_xs)
-            GzT = self.empty(2 * d.F, d.NS)
-            g_hsum = g_hsum.contiguous()
-            Yp = mu = var = part = None
-            eps = 0.0
-            if bn_sums is not None:
-                assert g_xs is not None
-                Yp, mu, var, eps = bn_sums
-                self._chk(Yp, mu, var)
-                part = self.empty((d.NS + 63) // 64, 32)
-            ws, wsb = self._wsargs(d)
-            _call("pfsgnn_target_bwd_fold", d.G, d.NF, d.NC, d.F, y.data_ptr(), _ptr(sc),
-                  _ptr(sh), Rs.data_ptr(), Wt1.data_ptr(), g_hsum.data_ptr(), GzT.data_ptr(),
-                  dWt1.data_ptr(), None, _ptr(g_xs), tmask.data_ptr(), _ptr(Yp), _ptr(mu),
-                  _ptr(var), float(eps), _ptr(part), ws, wsb, _stream())
-            return (GzT, None) if bn_sums is None else (GzT, None, part)
         if bn_sums is not None:
             assert g_xs is not None and not self._composed(d) and d.sp is None
-            Yp, mu, var, eps = bn_sums
-            self._chk(g_xs, Yp, mu, var)
-            GzT = self.empty(2 * d.F, d.NS)
-            gxe = self.empty(d.F, d.EP) if want_gxe else None
-            part = self.empty((d.NS + 63) // 64, 32)
-            g_hsum = g_hsum.contiguous()
-            ws, wsb = self._wsargs(d)
-            _call("pfsgnn_target_bwd_bn", d.G, d.NF, d.NC, d.F, y.data_ptr(), _ptr(sc), _ptr(sh),
-                  Rs.data_ptr(), Wt1.data_ptr(), g_hsum.data_ptr(), GzT.data_ptr(),
-                  dWt1.data_ptr(), _ptr(gxe), g_xs.data_ptr(), _ptr(tmask), Yp.data_ptr(),
-                  mu.data_ptr(), var.data_ptr(), float(eps), part.data_ptr(), ws, wsb, _stream())
-            return GzT, gxe, part
-        if self._composed(d):
+        elif self._composed(d):
             out = self._sp.target_bwd(d, y, sc, sh, Rs, Wt1, g_hsum, dWt1, want_gxe=want_gxe)
             if g_xs is not None:
                 self.lin_t(Wt1, 0, d.F, out[0], out=g_xs, add=True)
@@ -1260,12 +1275,16 @@ class HipBackend:
         self._chk(g_xs)
         GzT = self.empty(2 * d.F, d.NS)
         gxe = self.empty(d.F, d.EP) if want_gxe else None
-        g_hsum = g_hsum.contiguous()
-        ws, wsb = self._wsargs(d)
-        self._ecall("target_bwd", d, d.G, d.NF, d.NC, d.F, y.data_ptr(), _ptr(sc), _ptr(sh),
-              Rs.data_ptr(), Wt1.data_ptr(), g_hsum.data_ptr(), GzT.data_ptr(), dWt1.data_ptr(),
-              _ptr(gxe), _ptr(g_xs), _ptr(tmask), ws, wsb, _stream())
-        return GzT, gxe
+        Yp = mu = var = part = None
+        eps = 0.0
+        if bn_sums is not None:
+            Yp, mu, var, eps = bn_sums
+            self._chk(Yp, mu, var)
+            part = self.empty((d.NS + 63) // 64, 32)
+        self._ecall("target_bwd", d, y=y, sc=sc, sh=sh, Rs=Rs, Wt1=Wt1, g_hsum=g_hsum.contiguous(),
+                    GzT=GzT, dWt1=dWt1, gxe=gxe, g_xs=g_xs, tmask=tmask, bn_Yp=Yp, bn_mu=mu,
+                    bn_var=var, bn_eps=float(eps), bn_part=part, fold=int(fold))
+        return (GzT, gxe) if bn_sums is None else (GzT, gxe, part)
 
     def source_bwd(self, d, y, sc, sh, Qt, Ws1, Ws2, bs2, mean, coef, tpart, g_next, bnstat,
                    dWs1, dWs2, dbs2, bn2=None, g_xt=None, tmask=None, msg=None, dWt1=None):
@@ -1291,53 +1310,23 @@ class HipBackend:
         if tpart is not None:
             Rs, Wt1, g_hsum = tpart
             g_hsum = g_hsum.contiguous()
-        mu1 = inv1 = Sg = Sgx = None
+        mu1 = inv1 = Sg = Sgx = var1 = gamma = dg = db = a = g0 = g1 = None
+        n, eps = 0, 0.0
         if bnstat is not None:
             mu1, inv1 = bnstat
             if bn2 is None:
                 Sg, Sgx = self.empty(d.F), self.empty(d.F)
-        mean = mean.contiguous()
-        if g_next is not None:
-            g_next = g_next.contiguous()
-        ws, wsb = self._wsargs(d)
-        head = (d.G, d.NF, d.NC, d.F, y.data_ptr(), _ptr(sc), _ptr(sh), Qt.data_ptr(),
-                Ws1.data_ptr(), Ws2.data_ptr(), bs2.data_ptr(), mean.data_ptr(), coef.data_ptr(),
-                _ptr(Rs), _ptr(Wt1), _ptr(g_hsum), _ptr(g_next), _ptr(mu1), _ptr(inv1))
-        if dWt1 is not None:
-            var1 = gamma = a = g0 = g1 = dg = db = None
-            n, eps = 0, 0.0
-            if bn2 is not None:
-                assert bnstat is not None
-                gamma, var1, n, eps, dg, db = bn2
-                a, g0, g1 = self.empty(d.F), self.empty(d.F), self.empty(d.F)
-            _call("pfsgnn_source_bwd_fold", *head, _ptr(var1), _ptr(gamma), int(n), float(eps),
-                  g_tot.data_ptr(), GzS.data_ptr(), dWs1.data_ptr(), dWs2.data_ptr(),
-                  dbs2.data_ptr(), _ptr(Sg), _ptr(Sgx), _ptr(a), _ptr(g0), _ptr(g1), _ptr(dg),
-                  _ptr(db), _ptr(g_xt), tmask.data_ptr(), _ptr(msg), dWt1.data_ptr(), ws, wsb,
-                  _stream())
-            if bn2 is not None:
-                return g_tot, GzS, None, None, (a, g0, g1)
-            return g_tot, GzS, Sg, Sgx
         if bn2 is not None:
             assert bnstat is not None
             gamma, var1, n, eps, dg, db = bn2
             a, g0, g1 = self.empty(d.F), self.empty(d.F), self.empty(d.F)
-            tail = (var1.data_ptr(), gamma.data_ptr(), int(n), float(eps), g_tot.data_ptr(),
-                    GzS.data_ptr(), dWs1.data_ptr(), dWs2.data_ptr(), dbs2.data_ptr(),
-                    a.data_ptr(), g0.data_ptr(), g1.data_ptr(), dg.data_ptr(), db.data_ptr(),
-                    _ptr(g_xt), _ptr(tmask))
-            if msg is not None:
-                _call("pfsgnn_source_bwd_bn_msg", *head, *tail, msg.data_ptr(), ws, wsb, _stream())
-            else:
-                self._ecall("source_bwd_bn", d, *head, *tail, ws, wsb, _stream())
-            return g_tot, GzS, None, None, (a, g0, g1)
-        tail = (g_tot.data_ptr(), GzS.data_ptr(), dWs1.data_ptr(), dWs2.data_ptr(),
-                dbs2.data_ptr(), _ptr(Sg), _ptr(Sgx), _ptr(g_xt), _ptr(tmask))
-        if msg is not None:
-            _call("pfsgnn_source_bwd_msg", *head, *tail, msg.data_ptr(), ws, wsb, _stream())
-        else:
-            self._ecall("source_bwd", d, *head, *tail, ws, wsb, _stream())
-        return g_tot, GzS, Sg, Sgx
+        self._ecall("source_bwd", d, y=y, sc=sc, sh=sh, Qt=Qt, Ws1=Ws1, Ws2=Ws2, bs2=bs2,
+                    mean=mean.contiguous(), coef=coef, Rs=Rs, Wt1=Wt1, g_hsum=g_hsum,
+                    g_next=g_next.contiguous() if g_next is not None else None, mu1=mu1,
+                    inv1=inv1, var1=var1, gamma=gamma, n=int(n), eps=float(eps), g_tot=g_tot,
+                    GzS=GzS, dWs1=dWs1, dWs2=dWs2, dbs2=dbs2, Sg=Sg, Sgx=Sgx, alpha=a, gam0=g0,
+                    gam1=g1, dgamma=dg, dbeta=db, g_xt=g_xt, tmask=tmask, msg=msg, dWt1=dWt1)
+        return (g_tot, GzS, Sg, Sgx) if bn2 is None else (g_tot, GzS, None, None, (a, g0, g1))
 
     def edge_bn_grad_sums(self, d, g, y, mu1, inv1):
         if d.sp is not None:   # (slot tensors hold 0 at padding: the column sums hold)
@@ -1369,12 +1358,9 @@ class HipBackend:
             g_xs, g_xt = nodes
             self._chk(g_xs, g_xt)
             Vu = self.empty(d.F, d.NT)
-        ws, wsb = self._wsargs(d)
-        self._ecall("edge_mlp_bwd", d, d.G, d.NF, d.NC, d.F, g_tot.data_ptr(), alpha.data_ptr(),
-              gam0.data_ptr(), gam1.data_ptr(), y.data_ptr(), xe.data_ptr(), _ptr(xsc), _ptr(xsh),
-              Ps.data_ptr(), Pt.data_ptr(), W1.data_ptr(), W2.data_ptr(), dW1.data_ptr(),
-              dW2.data_ptr(), db2.data_ptr(), _ptr(gxe), GzEs.data_ptr(), GzEt.data_ptr(),
-              _ptr(g_xs), _ptr(g_xt), _ptr(Vu), ws, wsb, _stream())
+        self._ecall("edge_mlp_bwd", d, g_tot=g_tot, alpha=alpha, gam0=gam0, gam1=gam1, y=y, xe=xe,
+                    xsc=xsc, xsh=xsh, Ps=Ps, Pt=Pt, W1=W1, W2=W2, dW1=dW1, dW2=dW2, db2=db2,
+                    gxe=gxe, GzEs=GzEs, GzEt=GzEt, g_xs=g_xs, g_xt=g_xt, Vu=Vu)
         return (gxe, GzEs, GzEt) if nodes is None else (gxe, GzEs, GzEt, Vu)
 
     def edge_apply(self, d, y, sc, sh):

@@ -53,6 +53,132 @@ def test_block_tail_struct_layout_matches(lib):
     assert native.ClassBwd.g_hsum.offset == ctypes.sizeof(native.ClassBwd) - 8
 
 
+def test_edge_args_struct_layouts_match(lib):
+    """The six edge-op argument structs of native.py mirror include/pfsgnn.h:
+    same size as C reports, the last field where C puts it (it is a pointer, or
+    an int before the struct's tail padding: 8 bytes from the end either way),
+    and the head (G, NF, NC, F, sl) in front."""
+    import ctypes
+    from pfsgnn import native
+    last = {"edge_mlp_fwd": "inv2", "source_fwd": "msg", "target_fwd": "tmask",
+            "target_bwd": "fold", "source_bwd": "dWt1", "edge_mlp_bwd": "Vu"}
+    assert list(native.EDGE_ARGS) == list(last)
+    for op, (name, cls) in enumerate(native.EDGE_ARGS.items()):
+        assert lib.pfsgnn_edge_args_bytes(op) == ctypes.sizeof(cls), name
+        assert cls._fields_[-1][0] == last[name]
+        assert getattr(cls, last[name]).offset == ctypes.sizeof(cls) - 8, name
+        assert [f for f, _ in cls._fields_[:5]] == ["G", "NF", "NC", "F", "sl"]
+        assert cls.sl.offset == 16
+    assert lib.pfsgnn_edge_args_bytes(6) == 0
+    assert lib.pfsgnn_edge_args_bytes(-1) == 0
+
+
+# the edge ops' entry points before each op had one (argument structs)
+REMOVED_EDGE_ENTRY_POINTS = [
+    "pfsgnn_edge_mlp_fwd_bn", "pfsgnn_sl_edge_mlp_fwd", "pfsgnn_sl_edge_mlp_fwd_bn",
+    "pfsgnn_source_fwd_msg", "pfsgnn_sl_source_fwd", "pfsgnn_sl_target_fwd",
+    "pfsgnn_target_bwd_bn", "pfsgnn_target_bwd_fold", "pfsgnn_sl_target_bwd",
+    "pfsgnn_source_bwd_bn", "pfsgnn_source_bwd_msg", "pfsgnn_source_bwd_bn_msg",
+    "pfsgnn_source_bwd_fold", "pfsgnn_sl_source_bwd", "pfsgnn_sl_source_bwd_bn",
+    "pfsgnn_sl_edge_mlp_bwd"]
+
+
+def test_removed_edge_entry_points_are_gone(lib):
+    """Of the 22 former entry points of the six edge ops, the six base names
+    remain (with the struct signature) and the 16 variants are neither exported,
+    bound, nor named in the header."""
+    from pfsgnn import native
+    header = open(os.path.join(ROOT, "include", "pfsgnn.h")).read()
+    assert lib.pfsgnn_version().decode() == native.ABI_VERSION == "pfsgnn 0.2 gfx950"
+    for name in REMOVED_EDGE_ENTRY_POINTS:
+        assert not hasattr(lib, name), f"libpfsgnn.so still exports {name}"
+        assert name not in native._SIGS
+        assert not re.search(r"\b%s\b" % name, header), f"pfsgnn.h still names {name}"
+    for op in native.EDGE_ARGS:
+        assert hasattr(lib, "pfsgnn_" + op) and len(native._SIGS["pfsgnn_" + op][0]) == 4
+
+
+def test_library_of_another_abi_version_is_refused(tmp_path):
+    """A library left over from another tree (PFSGNN_LIB_PATH, a variant build)
+    can export the edge ops' names with the old signatures; the binding refuses
+    it by its version string instead of calling into it."""
+    import shutil
+    import sys
+    cc = shutil.which("cc") or shutil.which("gcc") or "/opt/rocm/llvm/bin/clang"
+    src = tmp_path / "old.c"
+    src.write_text('const char* pfsgnn_version(void) { return "pfsgnn 0.1 gfx950"; }\n')
+    so = tmp_path / "libpfsgnn_old.so"
+    subprocess.run([cc, "-shared", "-fPIC", "-o", str(so), str(src)], check=True)
+    code = ("import sys; sys.path.insert(0, %r)\n"
+            "from pfsgnn import native\n"
+            "try:\n    native.lib()\n"
+            "except native.NativeUnavailable as e:\n    print('REFUSED', e)\n" % PKG)
+    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, PFSGNN_LIB_PATH=str(so)),
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert "REFUSED" in r.stdout and "pfsgnn 0.1 gfx950" in r.stdout and "rebuild" in r.stdout
+
+
+def test_edge_ops_refuse_bad_arguments_before_any_launch(lib):
+    """Every argument check of an edge op runs before its first launch, so it
+    can be seen without a GPU: pointers are fake non-null addresses that are
+    never dereferenced.  Each refusal returns non-zero with an error text that
+    names the entry point (and the combination refused), and leaves no failure
+    state behind for the next call."""
+    import ctypes
+    from pfsgnn import native
+    FAKE = 0x1000
+    sliced = native.Sliced(fib=FAKE, base=FAKE, len=FAKE, cls=FAKE, pco=FAKE, EP=32, E=20,
+                           maxdeg=2)
+
+    def args(op, sl=False, **over):
+        """Valid dimensions, every pointer field set, scalars of a valid call."""
+        a = native.EDGE_ARGS[op](G=1, NF=16, NC=2, F=10,
+                                 sl=ctypes.pointer(sliced) if sl else None)
+        for f, ty in a._fields_[5:]:
+            if ty is ctypes.c_void_p:
+                setattr(a, f, FAKE)
+        if op == "source_bwd":
+            a.n = 32
+        # the optional parts that have no sliced form are off unless asked for
+        for f in {"source_fwd": ["msg"], "target_bwd": ["bn_part"],
+                  "source_bwd": ["msg", "dWt1"]}.get(op, []):
+            setattr(a, f, None)
+        for f, v in over.items():
+            setattr(a, f, v)
+        return a
+
+    def refused(op, a, *words):
+        fn = getattr(lib, "pfsgnn_" + op)
+        rc = fn(ctypes.byref(a) if a is not None else None, None, 0, None)
+        err = lib.pfsgnn_last_error().decode()
+        assert rc != 0, (op, words)
+        assert err.startswith("pfsgnn_" + op + ":"), err
+        for w in words:
+            assert w in err, (err, w)
+
+    for op in native.EDGE_ARGS:
+        refused(op, None, "null")                              # a NULL `a`
+    refused("edge_mlp_fwd", args("edge_mlp_fwd", y=None), "null")   # a required pointer NULL
+    refused("source_fwd", args("source_fwd", Qt=None), "null")
+    refused("target_fwd", args("target_fwd", hsum=None), "null")
+    refused("target_bwd", args("target_bwd", GzT=None), "null")
+    refused("source_bwd", args("source_bwd", coef=None), "null")
+    refused("edge_mlp_bwd", args("edge_mlp_bwd", GzEt=None), "null")
+    refused("source_fwd", args("source_fwd", sl=True, msg=FAKE), "sl", "msg")
+    refused("source_bwd", args("source_bwd", sl=True, msg=FAKE), "sl", "msg")
+    refused("target_bwd", args("target_bwd", sl=True, bn_part=FAKE), "sl", "bn_part")
+    refused("target_bwd", args("target_bwd", sl=True, fold=1), "sl", "fold")
+    refused("source_bwd", args("source_bwd", sl=True, dWt1=FAKE), "sl", "dWt1")
+    refused("source_bwd", args("source_bwd", dWt1=FAKE, tmask=None), "dWt1", "tmask")
+    refused("source_bwd", args("source_bwd", alpha=None), "gamma", "alpha")
+    refused("edge_mlp_fwd", args("edge_mlp_fwd", sc=None), "gamma", "sc")
+    refused("target_fwd", args("target_fwd", agg=None), "Wt2", "agg")
+    # no failure state is left behind: a valid host-only call succeeds
+    info = (ctypes.c_int * 4)()
+    assert lib.pfsgnn_edge_grid(1, 16, 2, info) == 0
+
+
 def test_workspace_query_is_host_only(lib):
     b = lib.pfsgnn_workspace_bytes(16, 2394, 128, 10)
     assert 1 << 20 < b < 1 << 31

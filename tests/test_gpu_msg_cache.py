@@ -1,5 +1,5 @@
-"""The SModel message cache (pfsgnn_msg_bytes / pfsgnn_source_fwd_msg /
-pfsgnn_source_bwd(_bn)_msg; off unless PFSGNN_MSG=1, read once per process):
+"""The SModel message cache (pfsgnn_msg_bytes / the `msg` field of
+pfsgnn_source_fwd and pfsgnn_source_bwd; off unless PFSGNN_MSG=1, read once per process):
 a training step with the forward's messages kept and read back by the
 backward must equal the recomputing step bit for bit, on both edge paths that
 keep it (mfma, mfma32) -- each arm in its own process."""

@@ -1,7 +1,7 @@
-"""The folded TModel / SModel edge backward pair (pfsgnn_target_bwd_fold +
-pfsgnn_source_bwd_fold: the mask-only target_bwd, and source_bwd taking
-dWt1[:, F:2F]) against today's pair
-(pfsgnn_target_bwd_bn + pfsgnn_source_bwd_bn) on the same inputs and against a
+"""The folded TModel / SModel edge backward pair (pfsgnn_target_bwd with
+`fold` + pfsgnn_source_bwd with `dWt1`: the mask-only target_bwd, and
+source_bwd taking dWt1[:, F:2F]) against today's pair
+(the same two entry points without `fold` / `dWt1`) on the same inputs and against a
 float64 torch evaluation of TModel's part, with zeroed gradient buffers.
 
 What source_bwd computed before is bitwise unchanged (g_tot, GzS, dWs1, dWs2,
@@ -13,8 +13,8 @@ since the fold issues the same operations in the same order from the other
 kernel, is bitwise today's too (a training step amplifies any other rounding
 within a few optimizer steps); two runs of the folded pair are bitwise
 identical.  At Fdim 16 the library keeps today's kernels behind the
-folded entry points (pfsgnn_tbwd_fold is 0 there), so those cases compare the
-same kernels through both pairs of entry points.
+folded arguments (pfsgnn_tbwd_fold is 0 there), so those cases compare the
+same kernels through both forms of the calls.
 """
 import pytest
 import torch
