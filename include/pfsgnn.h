@@ -918,6 +918,102 @@ int pfsgnn_sl_loss_bwd(const pfsgnn_sliced_t* sl, const int* pos_user, int G, in
                        float* dbd1, float* dWd2, float* dbd2, float* gxe, void* ws,
                        size_t ws_bytes, void* stream);
 
+/* The loss forward and backward behind ONE argument struct, complete and sliced
+ * batches alike; the positional entry points above are wrappers over these two
+ * and give the same bits.  Optional groups are left NULL / 0:
+ *   sl + pos_user   a sliced general batch (both, or neither: complete graphs);
+ *   seed_dev        a device seed overriding `seed`;
+ *   sf_dev          a device softfloor record overriding `sharpness` (below);
+ *   tt              the per-edge time;
+ *   bn_mu1, bn_inv1, bn_part   pfsgnn_loss_bwd_bn's sums (all three; complete
+ *                   graphs only).
+ * pfsgnn_loss_fwd_ex reads the inputs and writes n_prime, fiber_time, tmean,
+ * tvar (and tt); pfsgnn_loss_bwd_ex reads tmean, Gn, Gf, Gv (and gscale) and
+ * writes dWd1, dbd1, dWd2, dbd2, gxe (and bn_part).  Fields of the other
+ * direction are ignored.  Every argument check runs before the first launch.
+ *
+ * sf_dev: the reference anneals softfloor's sharpness every epoch
+ * (train.py:137, read at train.py:21-27); a captured step therefore reads it
+ * from the device.  sf_dev points at 4 floats (16-byte aligned), r =
+ * exp(-1/sharpness) (0 when sharpness == 0, train.py:26), atan(r / (1 - r)),
+ * 2 pi, 1 / pi, filled by pfsgnn_softfloor_record or pfsgnn_train_advance from
+ * a device float: r and the arctangent in double, rounded once to float. */
+typedef struct pfsgnn_loss_args {
+  int G, NF, NC, F;
+  const pfsgnn_sliced_t* sl;
+  const int* pos_user;
+  const float *y, *sc, *sh, *Wd1, *bd1, *Wd2, *bd2, *ci;
+  float scale, sharpness, noiselevel;
+  unsigned long long seed;
+  const unsigned long long* seed_dev;
+  const float* sf_dev;
+  float *n_prime, *fiber_time, *tmean, *tvar, *tt;
+  const float *Gn, *Gf, *Gv, *gscale;
+  float *dWd1, *dbd1, *dWd2, *dbd2, *gxe;
+  const float *bn_mu1, *bn_inv1;
+  float* bn_part;
+} pfsgnn_loss_args;
+/* sizeof(pfsgnn_loss_args), for bindings to check their struct layout */
+size_t pfsgnn_loss_args_bytes(void);
+int pfsgnn_loss_fwd_ex(const pfsgnn_loss_args* a, void* ws, size_t ws_bytes, void* stream);
+int pfsgnn_loss_bwd_ex(const pfsgnn_loss_args* a, void* ws, size_t ws_bytes, void* stream);
+/* sf [4] from the device float *sharpness (one thread; train.py:26) */
+int pfsgnn_softfloor_record(const float* sharpness, float* sf, void* stream);
+
+/* ---------------------------------------------------------------- training loop
+ * The per-epoch bookkeeping of train.py:133-165 as three small launches, so a
+ * whole epoch (these, the forward, the loss, the backward, pfsgnn_adam) is one
+ * captured graph with no host value in it.  Nothing here allocates,
+ * synchronises or uses atomics.
+ *
+ * pfsgnn_train_advance -- the head of the step (train.py:133, :137): one
+ * thread does *epoch += 1, *seed += 1, *sharpness = (float)(s0 + (s1 - s0) *
+ * epoch / nepochs) with the expression evaluated in double in exactly this
+ * order (numpy.float32 of the Python expression, bit for bit), and fills the
+ * softfloor record sf [4] from it (pfsgnn_softfloor_record in the same launch). */
+int pfsgnn_train_advance(long long* epoch, unsigned long long* seed, double s0, double s1,
+                         long long nepochs, float* sharpness, float* sf, void* stream);
+/* pfsgnn_train_record -- after pfsgnn_loss_finalize (train.py:138, :143-152).
+ * Sums loss / utils / variance [G] over the graphs in the order g = 0 .. G-1,
+ * writes losses / objective / variances [nepochs] at *epoch, the completion
+ * row comp [NT] = n_prime / (ci[1] / nfields) and, when completions != NULL,
+ * completions [NT][nepochs] at column *epoch.  An *epoch outside [0, nepochs)
+ * writes no history.  Then, in fp32, improved = utility > *best_utility &&
+ * *sharpness > min_sharp (a NaN utility: false, train.py:146); *improved = 0 /
+ * 1, and when 1 also *best_utility, *best_loss, *best_epoch (train.py:148-149). */
+typedef struct pfsgnn_train_record_args {
+  int G, NC;
+  long long nepochs;
+  const long long* epoch;
+  const float* sharpness;
+  const float *loss, *utils, *variance, *n_prime, *ci;
+  float nfields, min_sharp;
+  float *losses, *objective, *variances, *completions, *comp;
+  int* improved;
+  float *best_utility, *best_loss;
+  long long* best_epoch;
+} pfsgnn_train_record_args;
+size_t pfsgnn_train_record_args_bytes(void);
+int pfsgnn_train_record(const pfsgnn_train_record_args* a, void* stream);
+/* pfsgnn_copy_if -- after pfsgnn_adam (train.py:150-158: the best time, fiber
+ * time and completion row come from the forward before the update, the
+ * checkpointed weights and optimiser state are those after optimizer.step()).
+ * When *flag != 0, copies every job of the DEVICE array jobs [njobs]: n 4-byte
+ * words from src to dst (16-byte vector loads and stores where both are
+ * aligned so), grid-stride; when *flag == 0 every thread returns.  extra: a
+ * HOST array of up to PFSGNN_COPY_EXTRA_MAX further jobs that travel with the
+ * launch, for buffers whose address differs from step to step in an eager loop
+ * (the loss's time and fiber_time outputs); a capture fixes them.  max_n: the
+ * largest n of all jobs (sizes the grid).  Buffers must not overlap. */
+#define PFSGNN_COPY_EXTRA_MAX 4
+typedef struct pfsgnn_copy_job {
+  const void* src;
+  void* dst;
+  long long n;
+} pfsgnn_copy_job;
+int pfsgnn_copy_if(const int* flag, const pfsgnn_copy_job* jobs, int njobs,
+                   const pfsgnn_copy_job* extra, int nextra, long long max_n, void* stream);
+
 /* ---------------------------------------------------------------- layout
  * The reference takes an arbitrary edge_index [2][E] (int64, gnn.py:7).  A
  * complete bipartite batch in any edge order maps onto the canonical

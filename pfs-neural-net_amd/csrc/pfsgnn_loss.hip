@@ -55,13 +55,16 @@ __global__ __launch_bounds__(256) void k_loss_fwd(EdgeGeo geo, const float* __re
                                                   const float* __restrict__ Wd2,
                                                   const float* __restrict__ bd2,
                                                   const float* __restrict__ ci, float scale,
-                                                  SoftFloor sf, float noiselevel, uint64_t key0,
+                                                  SoftFloor sf0,
+                                                  const SoftFloor* __restrict__ sf_dev,
+                                                  float noiselevel, uint64_t key0,
                                                   const unsigned long long* __restrict__ seed_dev,
                                                   float* __restrict__ fiber_time,
                                                   float* __restrict__ tt_out,
                                                   float* __restrict__ part) {
   EDGE_PROLOGUE
   const uint64_t key = seed_dev ? pf_noise_key(*seed_dev) : key0;
+  const SoftFloor sf = sf_dev ? *sf_dev : sf0;   // wave-uniform: scalar loads
   __shared__ float scratch[4 * 64];
   __shared__ __attribute__((aligned(16))) DecW<F> dw;
   dw.load(Wd1, bd1, Wd2, bd2);
@@ -107,7 +110,9 @@ __global__ __launch_bounds__(256) void k_loss_bwd(EdgeGeo geo, const float* __re
                                                   const float* __restrict__ Wd2,
                                                   const float* __restrict__ bd2,
                                                   const float* __restrict__ ci, float scale,
-                                                  SoftFloor sf, float noiselevel, uint64_t key0,
+                                                  SoftFloor sf0,
+                                                  const SoftFloor* __restrict__ sf_dev,
+                                                  float noiselevel, uint64_t key0,
                                                   const unsigned long long* __restrict__ seed_dev,
                                                   const float* __restrict__ Gn,
                                                   const float* __restrict__ Gf,
@@ -123,6 +128,7 @@ __global__ __launch_bounds__(256) void k_loss_bwd(EdgeGeo geo, const float* __re
   using WG = WGrad<F, F + 1>;  // g_zd (x) [x, 1] -> dWd1 | dbd1
   EDGE_PROLOGUE
   const uint64_t key = seed_dev ? pf_noise_key(*seed_dev) : key0;
+  const SoftFloor sf = sf_dev ? *sf_dev : sf0;   // wave-uniform: scalar loads
   constexpr int LDS_N = (4 * WG::LDS_FLOATS > 4 * F * (F + 1)) ? 4 * WG::LDS_FLOATS
                                                                 : 4 * F * (F + 1);
   __shared__ float lds[LDS_N + 4 * (F + 1)];
@@ -361,34 +367,72 @@ EdgeGeo loss_geo(int G, int NF, int NC) {
 }  // namespace
 
 
+// The loss ops take one argument struct (pfsgnn_loss_args, include/pfsgnn.h);
+// the positional entry points below fill it and call the same code.  `where`
+// names the entry point the caller used in error texts.
+static int loss_fwd_impl(const char* where, const pfsgnn_loss_args& a, void* ws, size_t ws_bytes,
+                         void* stream) {
+  const int G = a.G, NF = a.NF, NC = a.NC, F = a.F;
+  if (int rc = check_dims(where, G, NF, NC, F)) return rc;
+  PF_REQUIRE(a.y && a.Wd1 && a.bd1 && a.Wd2 && a.bd2 && a.ci && a.n_prime && a.fiber_time &&
+                 a.tmean && a.tvar,
+             where, "null");
+  const EdgeGeo geo = loss_geo(G, NF, NC);
+  Ws w{reinterpret_cast<char*>(ws), ws_bytes};
+  float* part = w.take((size_t)G * geo.NFG * NC * 4);
+  float* ftp = geo.KS == 1 ? a.fiber_time : w.take((size_t)geo.KS * geo.NS);
+  PF_REQUIRE(part && ftp, where, "workspace too small");
+  hipStream_t st = as_stream(stream);
+  const SoftFloor sf = make_softfloor(a.sharpness);
+  const SoftFloor* sfd = reinterpret_cast<const SoftFloor*>(a.sf_dev);
+  const uint64_t key = pf_noise_key((uint64_t)a.seed);
+  { pf::Timer tm_("loss_fwd", st);
+  DISPATCH_F(F, hipLaunchKernelGGL(k_loss_fwd<FF>, dim3(edge_grid(geo)), dim3(256), 0, st, geo, a.y,
+                                   a.sc, a.sh, a.Wd1, a.bd1, a.Wd2, a.bd2, a.ci, a.scale, sf, sfd,
+                                   a.noiselevel, key, a.seed_dev, ftp, a.tt, part));
+  tm_.end(); }
+  if (geo.KS > 1)
+    hipLaunchKernelGGL(k_fiber_partial_sum, dim3((unsigned)((geo.NS + 255) / 256)), dim3(256), 0,
+                       st, ftp, geo.KS, geo.NS, a.fiber_time);
+  hipLaunchKernelGGL(k_loss_class_reduce<false>, dim3((G * NC + 3) / 4), dim3(256), 0, st, part, G,
+                     geo.NFG, NC, NF, a.n_prime, a.tmean, a.tvar);
+  return pf::check_launch(where);
+}
+
+// what every form of the struct must satisfy, before any launch
+static int loss_args_check(const char* where, const pfsgnn_loss_args* a) {
+  PF_REQUIRE(a, where, "null argument struct");
+  PF_REQUIRE(!a->sl == !a->pos_user, where,
+             "sl and pos_user go together (both set: a sliced general batch; both NULL: complete)");
+  const int nbn = (a->bn_mu1 != nullptr) + (a->bn_inv1 != nullptr) + (a->bn_part != nullptr);
+  PF_REQUIRE(nbn == 0 || nbn == 3, where, "bn_mu1, bn_inv1 and bn_part go together");
+  PF_REQUIRE(!(a->sl && nbn), where,
+             "sl with bn_part: the final BatchNorm's sums are not fused on a sliced batch");
+  return 0;
+}
+
+extern "C" size_t pfsgnn_loss_args_bytes(void) { return sizeof(pfsgnn_loss_args); }
+
+extern "C" int pfsgnn_loss_fwd_ex(const pfsgnn_loss_args* a, void* ws, size_t ws_bytes,
+                                  void* stream) {
+  if (int rc = loss_args_check("pfsgnn_loss_fwd_ex", a)) return rc;
+  if (a->sl) return pf_sl_loss_fwd("pfsgnn_loss_fwd_ex", *a, ws, ws_bytes, stream);
+  return loss_fwd_impl("pfsgnn_loss_fwd_ex", *a, ws, ws_bytes, stream);
+}
+
 extern "C" int pfsgnn_loss_fwd(int G, int NF, int NC, int F, const float* y, const float* sc,
                                const float* sh, const float* Wd1, const float* bd1,
                                const float* Wd2, const float* bd2, const float* ci, float scale,
                                float sharpness, float noiselevel, unsigned long long seed,
                                const unsigned long long* seed_dev, float* n_prime, float* fiber_time, float* tmean, float* tvar,
                                float* tt, void* ws, size_t ws_bytes, void* stream) {
-  if (int rc = check_dims("pfsgnn_loss_fwd", G, NF, NC, F)) return rc;
-  PF_REQUIRE(y && Wd1 && bd1 && Wd2 && bd2 && ci && n_prime && fiber_time && tmean && tvar,
-             "pfsgnn_loss_fwd", "null");
-  const EdgeGeo geo = loss_geo(G, NF, NC);
-  Ws w{reinterpret_cast<char*>(ws), ws_bytes};
-  float* part = w.take((size_t)G * geo.NFG * NC * 4);
-  float* ftp = geo.KS == 1 ? fiber_time : w.take((size_t)geo.KS * geo.NS);
-  PF_REQUIRE(part && ftp, "pfsgnn_loss_fwd", "workspace too small");
-  hipStream_t st = as_stream(stream);
-  const SoftFloor sf = make_softfloor(sharpness);
-  const uint64_t key = pf_noise_key((uint64_t)seed);
-  { pf::Timer tm_("loss_fwd", st);
-  DISPATCH_F(F, hipLaunchKernelGGL(k_loss_fwd<FF>, dim3(edge_grid(geo)), dim3(256), 0, st, geo, y,
-                                   sc, sh, Wd1, bd1, Wd2, bd2, ci, scale, sf, noiselevel, key, seed_dev,
-                                   ftp, tt, part));
-  tm_.end(); }
-  if (geo.KS > 1)
-    hipLaunchKernelGGL(k_fiber_partial_sum, dim3((unsigned)((geo.NS + 255) / 256)), dim3(256), 0,
-                       st, ftp, geo.KS, geo.NS, fiber_time);
-  hipLaunchKernelGGL(k_loss_class_reduce<false>, dim3((G * NC + 3) / 4), dim3(256), 0, st, part, G,
-                     geo.NFG, NC, NF, n_prime, tmean, tvar);
-  return pf::check_launch("pfsgnn_loss_fwd");
+  pfsgnn_loss_args a = {};
+  a.G = G; a.NF = NF; a.NC = NC; a.F = F;
+  a.y = y; a.sc = sc; a.sh = sh; a.Wd1 = Wd1; a.bd1 = bd1; a.Wd2 = Wd2; a.bd2 = bd2; a.ci = ci;
+  a.scale = scale; a.sharpness = sharpness; a.noiselevel = noiselevel;
+  a.seed = seed; a.seed_dev = seed_dev;
+  a.n_prime = n_prime; a.fiber_time = fiber_time; a.tmean = tmean; a.tvar = tvar; a.tt = tt;
+  return loss_fwd_impl("pfsgnn_loss_fwd", a, ws, ws_bytes, stream);
 }
 
 extern "C" int pfsgnn_loss_finalize(int G, int NF, int NC, const float* n_prime,
@@ -406,49 +450,71 @@ extern "C" int pfsgnn_loss_finalize(int G, int NF, int NC, const float* n_prime,
   return pf::check_launch("pfsgnn_loss_finalize");
 }
 
-static int loss_bwd_impl(int G, int NF, int NC, int F, const float* y, const float* sc,
-                         const float* sh, const float* Wd1, const float* bd1, const float* Wd2,
-                         const float* bd2, const float* ci, float scale, float sharpness,
-                         float noiselevel, unsigned long long seed,
-                         const unsigned long long* seed_dev, const float* Gn, const float* Gf,
-                         const float* Gv, const float* tmean, const float* gscale, float* dWd1,
-                         float* dbd1, float* dWd2, float* dbd2, float* gxe, const float* bn_mu1,
-                         const float* bn_inv1, float* bn_part, void* ws, size_t ws_bytes,
+static int loss_bwd_impl(const char* where, const pfsgnn_loss_args& a, void* ws, size_t ws_bytes,
                          void* stream) {
-  if (int rc = check_dims("pfsgnn_loss_bwd", G, NF, NC, F)) return rc;
-  PF_REQUIRE(y && Wd1 && bd1 && Wd2 && bd2 && ci && Gn && Gf && Gv && tmean && dWd1 && dbd1 &&
-                 dWd2 && dbd2 && gxe,
-             "pfsgnn_loss_bwd", "null");
+  const int G = a.G, NF = a.NF, NC = a.NC, F = a.F;
+  if (int rc = check_dims(where, G, NF, NC, F)) return rc;
+  PF_REQUIRE(a.y && a.Wd1 && a.bd1 && a.Wd2 && a.bd2 && a.ci && a.Gn && a.Gf && a.Gv && a.tmean &&
+                 a.dWd1 && a.dbd1 && a.dWd2 && a.dbd2 && a.gxe,
+             where, "null");
   const EdgeGeo geo = loss_geo(G, NF, NC);
   const size_t nb = geo.nblocks;
   Ws w{reinterpret_cast<char*>(ws), ws_bytes};
   float* pW = w.take(nb * F * (F + 1));
   float* pV = w.take(nb * (F + 1));
-  PF_REQUIRE(pW && pV, "pfsgnn_loss_bwd", "workspace too small");
+  PF_REQUIRE(pW && pV, where, "workspace too small");
   hipStream_t st = as_stream(stream);
-  const SoftFloor sf = make_softfloor(sharpness);
-  const uint64_t key = pf_noise_key((uint64_t)seed);
+  const SoftFloor sf = make_softfloor(a.sharpness);
+  const SoftFloor* sfd = reinterpret_cast<const SoftFloor*>(a.sf_dev);
+  const uint64_t key = pf_noise_key((uint64_t)a.seed);
   { pf::Timer tm_("loss_bwd", st);
-  if (bn_part) {
+  if (a.bn_part) {
     DISPATCH_F(F, hipLaunchKernelGGL((k_loss_bwd<FF, true>), dim3(edge_grid(geo)), dim3(256), 0, st,
-                                     geo, y, sc, sh, Wd1, bd1, Wd2, bd2, ci, scale, sf, noiselevel,
-                                     key, seed_dev, Gn, Gf, Gv, tmean, gscale, gxe, pW, pV, bn_mu1,
-                                     bn_inv1, bn_part));
+                                     geo, a.y, a.sc, a.sh, a.Wd1, a.bd1, a.Wd2, a.bd2, a.ci, a.scale,
+                                     sf, sfd, a.noiselevel, key, a.seed_dev, a.Gn, a.Gf, a.Gv,
+                                     a.tmean, a.gscale, a.gxe, pW, pV, a.bn_mu1, a.bn_inv1,
+                                     a.bn_part));
   } else {
     DISPATCH_F(F, hipLaunchKernelGGL((k_loss_bwd<FF, false>), dim3(edge_grid(geo)), dim3(256), 0, st,
-                                     geo, y, sc, sh, Wd1, bd1, Wd2, bd2, ci, scale, sf, noiselevel,
-                                     key, seed_dev, Gn, Gf, Gv, tmean, gscale, gxe, pW, pV, nullptr,
-                                     nullptr, nullptr));
+                                     geo, a.y, a.sc, a.sh, a.Wd1, a.bd1, a.Wd2, a.bd2, a.ci, a.scale,
+                                     sf, sfd, a.noiselevel, key, a.seed_dev, a.Gn, a.Gf, a.Gv,
+                                     a.tmean, a.gscale, a.gxe, pW, pV, nullptr, nullptr, nullptr));
   }
   tm_.end(); }
   {
-    RedDesc rd[4] = {{pW, (int)nb, (size_t)F * (F + 1), F + 1, F, F, dWd1, F, 1, 1.f},
-                     {pW + F, (int)nb, (size_t)F * (F + 1), F + 1, F, 1, dbd1, 1, 1, 1.f},
-                     {pV, (int)nb, (size_t)(F + 1), F, 1, F, dWd2, F, 1, 1.f},
-                     {pV + F, (int)nb, (size_t)(F + 1), 1, 1, 1, dbd2, 1, 1, 1.f}};
+    RedDesc rd[4] = {{pW, (int)nb, (size_t)F * (F + 1), F + 1, F, F, a.dWd1, F, 1, 1.f},
+                     {pW + F, (int)nb, (size_t)F * (F + 1), F + 1, F, 1, a.dbd1, 1, 1, 1.f},
+                     {pV, (int)nb, (size_t)(F + 1), F, 1, F, a.dWd2, F, 1, 1.f},
+                     {pV + F, (int)nb, (size_t)(F + 1), 1, 1, 1, a.dbd2, 1, 1, 1.f}};
     launch_reduce_multi(rd, 4, st);
   }
-  return pf::check_launch("pfsgnn_loss_bwd");
+  return pf::check_launch(where);
+}
+
+extern "C" int pfsgnn_loss_bwd_ex(const pfsgnn_loss_args* a, void* ws, size_t ws_bytes,
+                                  void* stream) {
+  if (int rc = loss_args_check("pfsgnn_loss_bwd_ex", a)) return rc;
+  if (a->sl) return pf_sl_loss_bwd("pfsgnn_loss_bwd_ex", *a, ws, ws_bytes, stream);
+  return loss_bwd_impl("pfsgnn_loss_bwd_ex", *a, ws, ws_bytes, stream);
+}
+
+static pfsgnn_loss_args loss_bwd_args(int G, int NF, int NC, int F, const float* y, const float* sc,
+                                      const float* sh, const float* Wd1, const float* bd1,
+                                      const float* Wd2, const float* bd2, const float* ci,
+                                      float scale, float sharpness, float noiselevel,
+                                      unsigned long long seed, const unsigned long long* seed_dev,
+                                      const float* Gn, const float* Gf, const float* Gv,
+                                      const float* tmean, const float* gscale, float* dWd1,
+                                      float* dbd1, float* dWd2, float* dbd2, float* gxe) {
+  pfsgnn_loss_args a = {};
+  a.G = G; a.NF = NF; a.NC = NC; a.F = F;
+  a.y = y; a.sc = sc; a.sh = sh; a.Wd1 = Wd1; a.bd1 = bd1; a.Wd2 = Wd2; a.bd2 = bd2; a.ci = ci;
+  a.scale = scale; a.sharpness = sharpness; a.noiselevel = noiselevel;
+  a.seed = seed; a.seed_dev = seed_dev;
+  a.tmean = const_cast<float*>(tmean);   // read only by the backward
+  a.Gn = Gn; a.Gf = Gf; a.Gv = Gv; a.gscale = gscale;
+  a.dWd1 = dWd1; a.dbd1 = dbd1; a.dWd2 = dWd2; a.dbd2 = dbd2; a.gxe = gxe;
+  return a;
 }
 
 extern "C" int pfsgnn_loss_bwd(int G, int NF, int NC, int F, const float* y, const float* sc,
@@ -460,9 +526,10 @@ extern "C" int pfsgnn_loss_bwd(int G, int NF, int NC, int F, const float* y, con
                                const float* tmean, const float* gscale, float* dWd1, float* dbd1,
                                float* dWd2, float* dbd2, float* gxe, void* ws, size_t ws_bytes,
                                void* stream) {
-  return loss_bwd_impl(G, NF, NC, F, y, sc, sh, Wd1, bd1, Wd2, bd2, ci, scale, sharpness,
-                       noiselevel, seed, seed_dev, Gn, Gf, Gv, tmean, gscale, dWd1, dbd1, dWd2,
-                       dbd2, gxe, nullptr, nullptr, nullptr, ws, ws_bytes, stream);
+  const pfsgnn_loss_args a = loss_bwd_args(G, NF, NC, F, y, sc, sh, Wd1, bd1, Wd2, bd2, ci, scale,
+                                           sharpness, noiselevel, seed, seed_dev, Gn, Gf, Gv, tmean,
+                                           gscale, dWd1, dbd1, dWd2, dbd2, gxe);
+  return loss_bwd_impl("pfsgnn_loss_bwd", a, ws, ws_bytes, stream);
 }
 
 extern "C" int pfsgnn_loss_bn_parts(int G, int NF, int NC) {
@@ -480,9 +547,11 @@ extern "C" int pfsgnn_loss_bwd_bn(int G, int NF, int NC, int F, const float* y, 
                                   const float* bn_mu1, const float* bn_inv1, float* bn_part,
                                   void* ws, size_t ws_bytes, void* stream) {
   PF_REQUIRE(bn_mu1 && bn_inv1 && bn_part, "pfsgnn_loss_bwd_bn", "null");
-  return loss_bwd_impl(G, NF, NC, F, y, sc, sh, Wd1, bd1, Wd2, bd2, ci, scale, sharpness,
-                       noiselevel, seed, seed_dev, Gn, Gf, Gv, tmean, gscale, dWd1, dbd1, dWd2,
-                       dbd2, gxe, bn_mu1, bn_inv1, bn_part, ws, ws_bytes, stream);
+  pfsgnn_loss_args a = loss_bwd_args(G, NF, NC, F, y, sc, sh, Wd1, bd1, Wd2, bd2, ci, scale,
+                                     sharpness, noiselevel, seed, seed_dev, Gn, Gf, Gv, tmean,
+                                     gscale, dWd1, dbd1, dWd2, dbd2, gxe);
+  a.bn_mu1 = bn_mu1; a.bn_inv1 = bn_inv1; a.bn_part = bn_part;
+  return loss_bwd_impl("pfsgnn_loss_bwd", a, ws, ws_bytes, stream);
 }
 
 extern "C" int pfsgnn_layout_analyze(const int64_t* edge_index, long long E, int G, int NF, int NC,

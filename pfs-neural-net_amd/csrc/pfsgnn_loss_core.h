@@ -27,6 +27,31 @@ static SoftFloor make_softfloor(float sharpness) {
   return s;
 }
 
+// The record from a DEVICE sharpness (a captured step anneals it per replay,
+// train.py:137): r = exp(-1/s) and corr = atan(r / (1 - r)) in double, each
+// rounded once to float.  s == 0 gives r = corr = 0 exactly (train.py:26); a
+// tiny s underflows to the same (exp(-2000) = 0 in double), never NaN.  One
+// thread calls it (k_softfloor_record, k_train_advance: pfsgnn_train.hip); the
+// loss kernels read the record through their sf_dev pointer.
+__device__ __forceinline__ void softfloor_fill(float sharpness, SoftFloor* out) {
+  const double s = (double)sharpness;
+  const double r = s == 0.0 ? 0.0 : exp(-1.0 / s);
+  const float pi = (float)M_PI;
+  out->r = (float)r;
+  out->corr = (float)atan(r / (1.0 - r));
+  out->two_pi = 2.0f * pi;
+  out->inv_pi = 1.0f / pi;
+}
+
+// the loss ops on a sliced general batch (pfsgnn_sl_loss.hip), reached from
+// pfsgnn_loss_fwd_ex / _bwd_ex (pfsgnn_loss.hip) when a->sl is set; `where`
+// names the entry point in error texts
+struct pfsgnn_loss_args;
+int pf_sl_loss_fwd(const char* where, const pfsgnn_loss_args& a, void* ws, size_t ws_bytes,
+                   void* stream);
+int pf_sl_loss_bwd(const char* where, const pfsgnn_loss_args& a, void* ws, size_t ws_bytes,
+                   void* stream);
+
 // decoder_e + softplus*scale + softfloor + clamp (train.py:42-49, gnn.py:307-312).
 // LOSS_FAST: sin / cos of 2 pi x as one sincospi of 2x (the reduction is exact
 // in revolutions, no large-argument path) and one reciprocal of T_i per edge

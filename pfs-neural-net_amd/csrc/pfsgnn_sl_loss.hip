@@ -152,11 +152,13 @@ __global__ __launch_bounds__(256) void ksl_loss_fwd(
     EdgeGeo geo, SlGeo sl, const int* __restrict__ pos_user, const float* __restrict__ y,
     const float* __restrict__ sc, const float* __restrict__ sh, const float* __restrict__ Wd1,
     const float* __restrict__ bd1, const float* __restrict__ Wd2, const float* __restrict__ bd2,
-    const float* __restrict__ ci, float scale, SoftFloor sf, float noiselevel, uint64_t key0,
+    const float* __restrict__ ci, float scale, SoftFloor sf0,
+    const SoftFloor* __restrict__ sf_dev, float noiselevel, uint64_t key0,
     const unsigned long long* __restrict__ seed_dev, float* __restrict__ fiber_time,
     float* __restrict__ tt_out, float* __restrict__ part) {
   SLL_PROLOGUE
   const uint64_t key = seed_dev ? pf_noise_key(*seed_dev) : key0;
+  const SoftFloor sf = sf_dev ? *sf_dev : sf0;   // wave-uniform: scalar loads
   __shared__ float crow[4][MAXC * CST];
   __shared__ int own[4][MAXC];
   __shared__ __attribute__((aligned(16))) DecW<F> dw;
@@ -229,7 +231,8 @@ __global__ __launch_bounds__(256) void ksl_loss_bwd(
     EdgeGeo geo, SlGeo sl, const int* __restrict__ pos_user, const float* __restrict__ y,
     const float* __restrict__ sc, const float* __restrict__ sh, const float* __restrict__ Wd1,
     const float* __restrict__ bd1, const float* __restrict__ Wd2, const float* __restrict__ bd2,
-    const float* __restrict__ ci, float scale, SoftFloor sf, float noiselevel, uint64_t key0,
+    const float* __restrict__ ci, float scale, SoftFloor sf0,
+    const SoftFloor* __restrict__ sf_dev, float noiselevel, uint64_t key0,
     const unsigned long long* __restrict__ seed_dev, const float* __restrict__ Gn,
     const float* __restrict__ Gf, const float* __restrict__ Gv, const float* __restrict__ tmean,
     const float* __restrict__ gscale, float* __restrict__ gxe, float* __restrict__ partW,
@@ -237,6 +240,7 @@ __global__ __launch_bounds__(256) void ksl_loss_bwd(
   using WG = WGrad<F, F + 1>;  // g_zd (x) [x, 1] -> dWd1 | dbd1
   SLL_PROLOGUE
   const uint64_t key = seed_dev ? pf_noise_key(*seed_dev) : key0;
+  const SoftFloor sf = sf_dev ? *sf_dev : sf0;   // wave-uniform: scalar loads
   constexpr int LDS_N = (4 * WG::LDS_FLOATS > 4 * F * (F + 1)) ? 4 * WG::LDS_FLOATS
                                                                 : 4 * F * (F + 1);
   __shared__ float lds[LDS_N + 4 * (F + 1)];
@@ -334,6 +338,40 @@ int check_sl(const char* where, const pfsgnn_sliced_t* sl, int G, int NF, int NC
 
 }  // namespace
 
+// the sliced forms of the loss ops behind pfsgnn_loss_fwd_ex / _bwd_ex
+// (pfsgnn_loss.hip) and the positional pfsgnn_sl_loss_* entry points below
+int pf_sl_loss_fwd(const char* where, const pfsgnn_loss_args& a, void* ws, size_t ws_bytes,
+                   void* stream) {
+  const int G = a.G, NF = a.NF, NC = a.NC, F = a.F;
+  if (int rc = check_sl(where, a.sl, G, NF, NC, F)) return rc;
+  PF_REQUIRE(a.pos_user && a.y && a.Wd1 && a.bd1 && a.Wd2 && a.bd2 && a.ci && a.n_prime &&
+                 a.fiber_time && a.tmean && a.tvar,
+             where, "null");
+  const SlGeo sg = sl_of(*a.sl);
+  const EdgeGeo geo = pfm::sl_geo(G, NF, NC, sg);
+  const int bpg = geo.NFG * geo.KS;   // class-partial rows per graph
+  LossWs w{reinterpret_cast<char*>(ws), ws_bytes};
+  float* part = w.take((size_t)G * bpg * NC * 4);
+  float* ftp = geo.KS == 1 ? a.fiber_time : w.take((size_t)geo.KS * geo.NS);
+  PF_REQUIRE(part && ftp, where, "workspace too small");
+  hipStream_t st = as_stream(stream);
+  const SoftFloor sf = make_softfloor(a.sharpness);
+  const SoftFloor* sfd = reinterpret_cast<const SoftFloor*>(a.sf_dev);
+  const uint64_t key = pf_noise_key((uint64_t)a.seed);
+  { pf::Timer tm_("loss_fwd", st);
+  LOSS_DISPATCH_F(F, hipLaunchKernelGGL(ksl_loss_fwd<FF>, dim3(geo.nblocks), dim3(256), 0, st, geo,
+                                        sg, a.pos_user, a.y, a.sc, a.sh, a.Wd1, a.bd1, a.Wd2, a.bd2,
+                                        a.ci, a.scale, sf, sfd, a.noiselevel, key, a.seed_dev, ftp,
+                                        a.tt, part));
+  tm_.end(); }
+  if (geo.KS > 1)
+    hipLaunchKernelGGL(ksl_fiber_partial_sum, dim3((unsigned)((geo.NS + 255) / 256)), dim3(256), 0,
+                       st, ftp, geo.KS, geo.NS, a.fiber_time);
+  hipLaunchKernelGGL(k_loss_class_reduce<true>, dim3((G * NC + 3) / 4), dim3(256), 0, st, part, G,
+                     bpg, NC, NF, a.n_prime, a.tmean, a.tvar);
+  return pf::check_launch(where);
+}
+
 extern "C" int pfsgnn_sl_loss_fwd(const pfsgnn_sliced_t* sl, const int* pos_user, int G, int NF,
                                   int NC, int F, const float* y, const float* sc, const float* sh,
                                   const float* Wd1, const float* bd1, const float* Wd2,
@@ -342,31 +380,13 @@ extern "C" int pfsgnn_sl_loss_fwd(const pfsgnn_sliced_t* sl, const int* pos_user
                                   const unsigned long long* seed_dev, float* n_prime,
                                   float* fiber_time, float* tmean, float* tvar, float* tt, void* ws,
                                   size_t ws_bytes, void* stream) {
-  if (int rc = check_sl("pfsgnn_sl_loss_fwd", sl, G, NF, NC, F)) return rc;
-  PF_REQUIRE(pos_user && y && Wd1 && bd1 && Wd2 && bd2 && ci && n_prime && fiber_time && tmean &&
-                 tvar,
-             "pfsgnn_sl_loss_fwd", "null");
-  const SlGeo sg = sl_of(*sl);
-  const EdgeGeo geo = pfm::sl_geo(G, NF, NC, sg);
-  const int bpg = geo.NFG * geo.KS;   // class-partial rows per graph
-  LossWs w{reinterpret_cast<char*>(ws), ws_bytes};
-  float* part = w.take((size_t)G * bpg * NC * 4);
-  float* ftp = geo.KS == 1 ? fiber_time : w.take((size_t)geo.KS * geo.NS);
-  PF_REQUIRE(part && ftp, "pfsgnn_sl_loss_fwd", "workspace too small");
-  hipStream_t st = as_stream(stream);
-  const SoftFloor sf = make_softfloor(sharpness);
-  const uint64_t key = pf_noise_key((uint64_t)seed);
-  { pf::Timer tm_("loss_fwd", st);
-  LOSS_DISPATCH_F(F, hipLaunchKernelGGL(ksl_loss_fwd<FF>, dim3(geo.nblocks), dim3(256), 0, st, geo,
-                                        sg, pos_user, y, sc, sh, Wd1, bd1, Wd2, bd2, ci, scale, sf,
-                                        noiselevel, key, seed_dev, ftp, tt, part));
-  tm_.end(); }
-  if (geo.KS > 1)
-    hipLaunchKernelGGL(ksl_fiber_partial_sum, dim3((unsigned)((geo.NS + 255) / 256)), dim3(256), 0,
-                       st, ftp, geo.KS, geo.NS, fiber_time);
-  hipLaunchKernelGGL(k_loss_class_reduce<true>, dim3((G * NC + 3) / 4), dim3(256), 0, st, part, G,
-                     bpg, NC, NF, n_prime, tmean, tvar);
-  return pf::check_launch("pfsgnn_sl_loss_fwd");
+  pfsgnn_loss_args a = {};
+  a.G = G; a.NF = NF; a.NC = NC; a.F = F; a.sl = sl; a.pos_user = pos_user;
+  a.y = y; a.sc = sc; a.sh = sh; a.Wd1 = Wd1; a.bd1 = bd1; a.Wd2 = Wd2; a.bd2 = bd2; a.ci = ci;
+  a.scale = scale; a.sharpness = sharpness; a.noiselevel = noiselevel;
+  a.seed = seed; a.seed_dev = seed_dev;
+  a.n_prime = n_prime; a.fiber_time = fiber_time; a.tmean = tmean; a.tvar = tvar; a.tt = tt;
+  return pf_sl_loss_fwd("pfsgnn_sl_loss_fwd", a, ws, ws_bytes, stream);
 }
 
 extern "C" int pfsgnn_sl_loss_finalize(const pfsgnn_sliced_t* sl, const int* pos_user, int G,
@@ -386,6 +406,40 @@ extern "C" int pfsgnn_sl_loss_finalize(const pfsgnn_sliced_t* sl, const int* pos
   return pf::check_launch("pfsgnn_sl_loss_finalize");
 }
 
+int pf_sl_loss_bwd(const char* where, const pfsgnn_loss_args& a, void* ws, size_t ws_bytes,
+                   void* stream) {
+  const int G = a.G, NF = a.NF, NC = a.NC, F = a.F;
+  if (int rc = check_sl(where, a.sl, G, NF, NC, F)) return rc;
+  PF_REQUIRE(a.pos_user && a.y && a.Wd1 && a.bd1 && a.Wd2 && a.bd2 && a.ci && a.Gn && a.Gf &&
+                 a.Gv && a.tmean && a.dWd1 && a.dbd1 && a.dWd2 && a.dbd2 && a.gxe,
+             where, "null");
+  const SlGeo sg = sl_of(*a.sl);
+  const EdgeGeo geo = pfm::sl_geo(G, NF, NC, sg);
+  const size_t nb = geo.nblocks;
+  LossWs w{reinterpret_cast<char*>(ws), ws_bytes};
+  float* pW = w.take(nb * F * (F + 1));
+  float* pV = w.take(nb * (F + 1));
+  PF_REQUIRE(pW && pV, where, "workspace too small");
+  hipStream_t st = as_stream(stream);
+  const SoftFloor sf = make_softfloor(a.sharpness);
+  const SoftFloor* sfd = reinterpret_cast<const SoftFloor*>(a.sf_dev);
+  const uint64_t key = pf_noise_key((uint64_t)a.seed);
+  { pf::Timer tm_("loss_bwd", st);
+  LOSS_DISPATCH_F(F, hipLaunchKernelGGL(ksl_loss_bwd<FF>, dim3(geo.nblocks), dim3(256), 0, st, geo,
+                                        sg, a.pos_user, a.y, a.sc, a.sh, a.Wd1, a.bd1, a.Wd2, a.bd2,
+                                        a.ci, a.scale, sf, sfd, a.noiselevel, key, a.seed_dev, a.Gn,
+                                        a.Gf, a.Gv, a.tmean, a.gscale, a.gxe, pW, pV));
+  tm_.end(); }
+  {
+    RedDesc rd[4] = {{pW, (int)nb, (size_t)F * (F + 1), F + 1, F, F, a.dWd1, F, 1, 1.f},
+                     {pW + F, (int)nb, (size_t)F * (F + 1), F + 1, F, 1, a.dbd1, 1, 1, 1.f},
+                     {pV, (int)nb, (size_t)(F + 1), F, 1, F, a.dWd2, F, 1, 1.f},
+                     {pV + F, (int)nb, (size_t)(F + 1), 1, 1, 1, a.dbd2, 1, 1, 1.f}};
+    launch_reduce_multi(rd, 4, st);
+  }
+  return pf::check_launch(where);
+}
+
 extern "C" int pfsgnn_sl_loss_bwd(const pfsgnn_sliced_t* sl, const int* pos_user, int G, int NF,
                                   int NC, int F, const float* y, const float* sc, const float* sh,
                                   const float* Wd1, const float* bd1, const float* Wd2,
@@ -396,32 +450,13 @@ extern "C" int pfsgnn_sl_loss_bwd(const pfsgnn_sliced_t* sl, const int* pos_user
                                   const float* gscale, float* dWd1, float* dbd1, float* dWd2,
                                   float* dbd2, float* gxe, void* ws, size_t ws_bytes,
                                   void* stream) {
-  if (int rc = check_sl("pfsgnn_sl_loss_bwd", sl, G, NF, NC, F)) return rc;
-  PF_REQUIRE(pos_user && y && Wd1 && bd1 && Wd2 && bd2 && ci && Gn && Gf && Gv && tmean && dWd1 &&
-                 dbd1 && dWd2 && dbd2 && gxe,
-             "pfsgnn_sl_loss_bwd", "null");
-  const SlGeo sg = sl_of(*sl);
-  const EdgeGeo geo = pfm::sl_geo(G, NF, NC, sg);
-  const size_t nb = geo.nblocks;
-  LossWs w{reinterpret_cast<char*>(ws), ws_bytes};
-  float* pW = w.take(nb * F * (F + 1));
-  float* pV = w.take(nb * (F + 1));
-  PF_REQUIRE(pW && pV, "pfsgnn_sl_loss_bwd", "workspace too small");
-  hipStream_t st = as_stream(stream);
-  const SoftFloor sf = make_softfloor(sharpness);
-  const uint64_t key = pf_noise_key((uint64_t)seed);
-  { pf::Timer tm_("loss_bwd", st);
-  LOSS_DISPATCH_F(F, hipLaunchKernelGGL(ksl_loss_bwd<FF>, dim3(geo.nblocks), dim3(256), 0, st, geo,
-                                        sg, pos_user, y, sc, sh, Wd1, bd1, Wd2, bd2, ci, scale, sf,
-                                        noiselevel, key, seed_dev, Gn, Gf, Gv, tmean, gscale, gxe,
-                                        pW, pV));
-  tm_.end(); }
-  {
-    RedDesc rd[4] = {{pW, (int)nb, (size_t)F * (F + 1), F + 1, F, F, dWd1, F, 1, 1.f},
-                     {pW + F, (int)nb, (size_t)F * (F + 1), F + 1, F, 1, dbd1, 1, 1, 1.f},
-                     {pV, (int)nb, (size_t)(F + 1), F, 1, F, dWd2, F, 1, 1.f},
-                     {pV + F, (int)nb, (size_t)(F + 1), 1, 1, 1, dbd2, 1, 1, 1.f}};
-    launch_reduce_multi(rd, 4, st);
-  }
-  return pf::check_launch("pfsgnn_sl_loss_bwd");
+  pfsgnn_loss_args a = {};
+  a.G = G; a.NF = NF; a.NC = NC; a.F = F; a.sl = sl; a.pos_user = pos_user;
+  a.y = y; a.sc = sc; a.sh = sh; a.Wd1 = Wd1; a.bd1 = bd1; a.Wd2 = Wd2; a.bd2 = bd2; a.ci = ci;
+  a.scale = scale; a.sharpness = sharpness; a.noiselevel = noiselevel;
+  a.seed = seed; a.seed_dev = seed_dev;
+  a.tmean = const_cast<float*>(tmean);   // read only by the backward
+  a.Gn = Gn; a.Gf = Gf; a.Gv = Gv; a.gscale = gscale;
+  a.dWd1 = dWd1; a.dbd1 = dbd1; a.dWd2 = dWd2; a.dbd2 = dbd2; a.gxe = gxe;
+  return pf_sl_loss_bwd("pfsgnn_sl_loss_bwd", a, ws, ws_bytes, stream);
 }

@@ -846,8 +846,14 @@ class Engine:
         channel-major [>=2, NT] (row 0 = T_i hours per visit, row 1 = N_i).
         On a sliced general batch (``d.sp.sl``) the backend runs the
         edge_index-indexed form (include/pfsgnn.h, pfsgnn_sl_loss_fwd): xe3 in
-        slot order, ``time`` in the caller's edge order."""
+        slot order, ``time`` in the caller's edge order.  ``sharpness``: a
+        Python number, or a device tensor read in-kernel -- one float32 (its
+        softfloor record is made here, once; the backward reuses it) or an
+        already filled record [4] (``be.softfloor_record`` / ``train_advance``)."""
         be = self.be
+        if (isinstance(sharpness, torch.Tensor) and sharpness.numel() == 1
+                and hasattr(be, "softfloor_record")):
+            sharpness = be.softfloor_record(sharpness)
         y, sc, sh = xe3
         scale = total_time / d.NC                     # TOTAL_TIME/NCLASSES, train.py:42
         dec = [P["decoder_e.0.weight"], P["decoder_e.0.bias"], P["decoder_e.2.weight"], P["decoder_e.2.bias"]]

@@ -190,6 +190,32 @@ class EdgeMlpBwdArgs(ctypes.Structure):
                         "Vu"))
 
 
+class LossArgs(ctypes.Structure):
+    """pfsgnn_loss_args: the loss forward / backward on a complete or sliced
+    batch; optional groups (sl + pos_user, seed_dev, sf_dev, tt, the bn_* group)
+    stay NULL."""
+    _fields_ = ([("G", I), ("NF", I), ("NC", I), ("F", I), ("sl", SLP)]
+                + _ptrs("pos_user", "y", "sc", "sh", "Wd1", "bd1", "Wd2", "bd2", "ci")
+                + [("scale", FL), ("sharpness", FL), ("noiselevel", FL), ("seed", ULL)]
+                + _ptrs("seed_dev", "sf_dev", "n_prime", "fiber_time", "tmean", "tvar", "tt",
+                        "Gn", "Gf", "Gv", "gscale", "dWd1", "dbd1", "dWd2", "dbd2", "gxe",
+                        "bn_mu1", "bn_inv1", "bn_part"))
+
+
+class TrainRecordArgs(ctypes.Structure):
+    """pfsgnn_train_record_args: an epoch's history rows and best-tracking."""
+    _fields_ = ([("G", I), ("NC", I), ("nepochs", LL)]
+                + _ptrs("epoch", "sharpness", "loss", "utils", "variance", "n_prime", "ci")
+                + [("nfields", FL), ("min_sharp", FL)]
+                + _ptrs("losses", "objective", "variances", "completions", "comp", "improved",
+                        "best_utility", "best_loss", "best_epoch"))
+
+
+class CopyJob(ctypes.Structure):
+    """pfsgnn_copy_job: n 4-byte words from src to dst."""
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("n", LL)]
+
+
 # op name -> argument struct, in the order of the PFSGNN_OP_* codes
 EDGE_ARGS = {"edge_mlp_fwd": EdgeMlpFwdArgs, "source_fwd": SourceFwdArgs,
              "target_fwd": TargetFwdArgs, "target_bwd": TargetBwdArgs,
@@ -300,6 +326,14 @@ _SIGS = {
     "pfsgnn_edges_from_slots": ([P, P, P, LL, LL, I, P, I, P, P], I),
     "pfsgnn_sl_tmask_bytes": ([SLP, I], SZ),
     "pfsgnn_edge_args_bytes": ([I], SZ),
+    "pfsgnn_loss_args_bytes": ([], SZ),
+    "pfsgnn_loss_fwd_ex": ([ctypes.POINTER(LossArgs), P, SZ, P], I),
+    "pfsgnn_loss_bwd_ex": ([ctypes.POINTER(LossArgs), P, SZ, P], I),
+    "pfsgnn_softfloor_record": ([P, P, P], I),
+    "pfsgnn_train_advance": ([P, P, ctypes.c_double, ctypes.c_double, LL, P, P, P], I),
+    "pfsgnn_train_record_args_bytes": ([], SZ),
+    "pfsgnn_train_record": ([ctypes.POINTER(TrainRecordArgs), P], I),
+    "pfsgnn_copy_if": ([P, P, I, ctypes.POINTER(CopyJob), I, LL, P], I),
 }
 for _op, _cls in EDGE_ARGS.items():
     _SIGS["pfsgnn_" + _op] = ([ctypes.POINTER(_cls), P, SZ, P], I)
@@ -333,6 +367,12 @@ def lib():
             fn = getattr(L, name)
             fn.argtypes = args
             fn.restype = ret
+        for query, cls in (("pfsgnn_loss_args_bytes", LossArgs),
+                           ("pfsgnn_train_record_args_bytes", TrainRecordArgs)):
+            if getattr(L, query)() != ctypes.sizeof(cls):
+                raise NativeUnavailable(
+                    f"{_LIB_PATH}: {query}() = {getattr(L, query)()} but this binding's "
+                    f"{cls.__name__} has {ctypes.sizeof(cls)} bytes: rebuild the library")
         _lib = L
         path = os.environ.get("PFSGNN_EDGE_PATH")
         if path:
@@ -1381,6 +1421,105 @@ class HipBackend:
             return 0, seed.data_ptr()
         return int(seed) & ((1 << 64) - 1), None
 
+    def softfloor_record(self, sharpness):
+        """softfloor's coefficients [4] (r, atan(r / (1 - r)), 2 pi, 1 / pi) from a
+        device float32 sharpness, on the device (pfsgnn_softfloor_record): what
+        the loss kernels read when the sharpness is a tensor."""
+        if (not isinstance(sharpness, torch.Tensor) or not sharpness.is_cuda
+                or sharpness.dtype != torch.float32 or sharpness.numel() != 1):
+            raise ValueError("a tensor sharpness must be one float32 on the device")
+        rec = self.empty(4)
+        _call("pfsgnn_softfloor_record", sharpness.data_ptr(), rec.data_ptr(), _stream())
+        return rec
+
+    def _sharp_args(self, sharpness):
+        """(value, device record, keep-alive): a Python number goes by value; a
+        device tensor is read by the kernels -- a filled record [4]
+        (softfloor_record, train_advance), or one float32 sharpness, whose
+        record is made here."""
+        if isinstance(sharpness, torch.Tensor):
+            rec = sharpness if sharpness.numel() == 4 else self.softfloor_record(sharpness)
+            if (not rec.is_cuda or rec.dtype != torch.float32 or not rec.is_contiguous()
+                    or rec.data_ptr() % 16):
+                raise ValueError("a softfloor record must be 4 contiguous float32 on the device, "
+                                 "16-byte aligned")
+            return 0.0, rec.data_ptr(), rec
+        return float(sharpness), None, None
+
+    def _loss_args(self, d, sl, y, sc, sh, Wd1, bd1, Wd2, bd2, ci, scale, sharpness, noiselevel,
+                   seed):
+        """pfsgnn_loss_args with the inputs both directions share."""
+        a = LossArgs(G=d.G, NF=d.NF, NC=d.NC, F=d.F)
+        if sl is not None:
+            a.sl, a.pos_user = sl.ref, sl.pos_user.data_ptr()
+        a.y, a.sc, a.sh = y.data_ptr(), _ptr(sc), _ptr(sh)
+        a.Wd1, a.bd1, a.Wd2, a.bd2 = Wd1.data_ptr(), bd1.data_ptr(), Wd2.data_ptr(), bd2.data_ptr()
+        a.ci = ci.data_ptr()
+        a.scale, a.noiselevel = float(scale), float(noiselevel)
+        a.sharpness, a.sf_dev, a._keep = self._sharp_args(sharpness)
+        a.seed, a.seed_dev = self._seed_args(seed)
+        return a
+
+    # ------------------------------------------------------------ training loop
+    def train_advance(self, epoch, seed, s0, s1, nepochs, sharpness, sf):
+        """epoch += 1, seed += 1, sharpness = s0 + (s1 - s0) * epoch / nepochs
+        (train.py:137, in double, rounded once) and its softfloor record ``sf``
+        [4], in one launch (pfsgnn_train_advance)."""
+        assert epoch.dtype == torch.int64 and seed.dtype == torch.int64
+        assert sharpness.dtype == torch.float32 and sf.dtype == torch.float32 and sf.numel() == 4
+        _call("pfsgnn_train_advance", epoch.data_ptr(), seed.data_ptr(), float(s0), float(s1),
+              int(nepochs), sharpness.data_ptr(), sf.data_ptr(), _stream())
+
+    def train_record(self, d, nepochs, epoch, sharpness, loss, utils, variance, n_prime, ci,
+                     nfields, min_sharp, losses, objective, variances, completions, comp, improved,
+                     best_utility, best_loss, best_epoch):
+        """An epoch's history rows and best-tracking (pfsgnn_train_record);
+        ``completions`` [NT, nepochs] or None."""
+        self._chk(loss, utils, variance, n_prime, ci, losses, objective, variances, completions, comp,
+                  best_utility, best_loss, sharpness)
+        assert min(losses.numel(), objective.numel(), variances.numel()) >= nepochs
+        assert completions is None or completions.numel() >= d.NT * nepochs
+        assert comp.numel() >= d.NT and ci.numel() >= 2 * d.NT and n_prime.numel() >= d.NT
+        assert improved.dtype == torch.int32 and best_epoch.dtype == epoch.dtype == torch.int64
+        a = TrainRecordArgs(G=d.G, NC=d.NC, nepochs=int(nepochs), nfields=float(nfields),
+                            min_sharp=float(min_sharp))
+        for k, v in dict(epoch=epoch, sharpness=sharpness, loss=loss, utils=utils,
+                         variance=variance, n_prime=n_prime, ci=ci, losses=losses,
+                         objective=objective, variances=variances, completions=completions,
+                         comp=comp, improved=improved, best_utility=best_utility,
+                         best_loss=best_loss, best_epoch=best_epoch).items():
+            setattr(a, k, _ptr(v))
+        _call("pfsgnn_train_record", ctypes.byref(a), _stream())
+
+    @staticmethod
+    def _copy_job_array(pairs):
+        """(pfsgnn_copy_job array, largest word count) of (src, dst) tensor pairs
+        of equal byte size (a multiple of 4)."""
+        jobs = (CopyJob * max(len(pairs), 1))()
+        nmax = 0
+        for j, (s, t) in zip(jobs, pairs):
+            nb = s.numel() * s.element_size()
+            assert s.is_contiguous() and t.is_contiguous() and s.is_cuda and t.is_cuda
+            assert nb == t.numel() * t.element_size() and nb % 4 == 0, (s.shape, t.shape)
+            j.src, j.dst, j.n = s.data_ptr(), t.data_ptr(), nb // 4
+            nmax = max(nmax, nb // 4)
+        return jobs, nmax
+
+    def copy_jobs(self, pairs):
+        """The device job list of ``copy_if`` for buffers at fixed addresses."""
+        jobs, nmax = self._copy_job_array(pairs)
+        host = torch.frombuffer(bytearray(bytes(jobs)), dtype=torch.uint8)
+        return dict(dev=host.to(self.device), n=len(pairs), nmax=nmax, keep=list(pairs))
+
+    def copy_if(self, flag, jobs, extra=()):
+        """Every job of ``jobs`` (copy_jobs) and of the (src, dst) pairs ``extra``
+        (at most 4: buffers whose address may differ from step to step) when the
+        device int32 ``flag`` is set, in one launch (pfsgnn_copy_if)."""
+        assert flag.dtype == torch.int32 and flag.is_cuda
+        xs, xmax = self._copy_job_array(list(extra))
+        _call("pfsgnn_copy_if", flag.data_ptr(), jobs["dev"].data_ptr(), jobs["n"], xs, len(extra),
+              max(jobs["nmax"], xmax), _stream())
+
     @staticmethod
     def _loss_layout(d):
         """The sliced layout of a general batch (None: a complete batch).  The
@@ -1415,12 +1554,12 @@ class HipBackend:
         tt = self.empty(d.E) if want_time else None
         ci = ci.contiguous()
         assert sl is None or tuple(y.shape) == (d.F, sl.EP), (tuple(y.shape), d.F, sl.EP)
+        a = self._loss_args(d, sl, y, sc, sh, Wd1, bd1, Wd2, bd2, ci, scale, sharpness, noiselevel,
+                            seed)
+        a.n_prime, a.fiber_time = n_prime.data_ptr(), fiber_time.data_ptr()
+        a.tmean, a.tvar, a.tt = tmean.data_ptr(), tvar.data_ptr(), _ptr(tt)
         ws, wsb = self._wsargs(d)
-        self._lcall("loss_fwd", sl, d.G, d.NF, d.NC, d.F, y.data_ptr(), _ptr(sc), _ptr(sh),
-                    Wd1.data_ptr(), bd1.data_ptr(), Wd2.data_ptr(), bd2.data_ptr(), ci.data_ptr(),
-                    float(scale), float(sharpness), float(noiselevel), *self._seed_args(seed),
-                    n_prime.data_ptr(), fiber_time.data_ptr(), tmean.data_ptr(), tvar.data_ptr(),
-                    _ptr(tt), ws, wsb, _stream())
+        _call("pfsgnn_loss_fwd_ex", ctypes.byref(a), ws, wsb, _stream())
         return n_prime, fiber_time, tmean, tvar, tt
 
     def loss_finalize(self, d, n_prime, fiber_time, tvar, ci, pclass, pfiber, total_time, nfields,
@@ -1453,26 +1592,22 @@ class HipBackend:
         elif gscale != 1.0:
             gs = torch.full((1,), float(gscale), dtype=torch.float32, device=self.device)
         ci = ci.contiguous()
-        ws, wsb = self._wsargs(d)
+        a = self._loss_args(d, sl, y, sc, sh, Wd1, bd1, Wd2, bd2, ci, scale, sharpness, noiselevel,
+                            seed)
+        a.Gn, a.Gf, a.Gv = Gn.data_ptr(), Gf.data_ptr(), Gv.data_ptr()
+        a.tmean, a.gscale = tmean.data_ptr(), _ptr(gs)
+        a.dWd1, a.dbd1, a.dWd2, a.dbd2 = (dWd1.data_ptr(), dbd1.data_ptr(), dWd2.data_ptr(),
+                                          dbd2.data_ptr())
+        a.gxe = gxe.data_ptr()
+        part = None
         if bn is not None:
             mu1, inv1 = bn
             self._chk(mu1, inv1)
             part = self.empty(lib().pfsgnn_loss_bn_parts(d.G, d.NF, d.NC), 2 * d.F)
-            _call("pfsgnn_loss_bwd_bn", d.G, d.NF, d.NC, d.F, y.data_ptr(), _ptr(sc), _ptr(sh),
-                  Wd1.data_ptr(), bd1.data_ptr(), Wd2.data_ptr(), bd2.data_ptr(), ci.data_ptr(),
-                  float(scale), float(sharpness), float(noiselevel), *self._seed_args(seed),
-                  Gn.data_ptr(), Gf.data_ptr(), Gv.data_ptr(), tmean.data_ptr(), _ptr(gs),
-                  dWd1.data_ptr(), dbd1.data_ptr(), dWd2.data_ptr(), dbd2.data_ptr(),
-                  gxe.data_ptr(), mu1.data_ptr(), inv1.data_ptr(), part.data_ptr(), ws, wsb,
-                  _stream())
-            return gxe, part
-        self._lcall("loss_bwd", sl, d.G, d.NF, d.NC, d.F, y.data_ptr(), _ptr(sc), _ptr(sh),
-                    Wd1.data_ptr(), bd1.data_ptr(), Wd2.data_ptr(), bd2.data_ptr(), ci.data_ptr(),
-                    float(scale), float(sharpness), float(noiselevel), *self._seed_args(seed),
-                    Gn.data_ptr(), Gf.data_ptr(), Gv.data_ptr(), tmean.data_ptr(), _ptr(gs),
-                    dWd1.data_ptr(), dbd1.data_ptr(), dWd2.data_ptr(), dbd2.data_ptr(),
-                    gxe.data_ptr(), ws, wsb, _stream())
-        return gxe
+            a.bn_mu1, a.bn_inv1, a.bn_part = mu1.data_ptr(), inv1.data_ptr(), part.data_ptr()
+        ws, wsb = self._wsargs(d)
+        _call("pfsgnn_loss_bwd_ex", ctypes.byref(a), ws, wsb, _stream())
+        return gxe if bn is None else (gxe, part)
 
     # ------------------------------------------------------------ graph building
     def build_complete(self, G, NF, NC, order=0):

@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from . import config
+from . import gnn as _gnn
 from .engine import Dims
 from .gnn import GNN, BipartiteData, backend
 
@@ -61,7 +62,10 @@ class _LossFn(torch.autograd.Function):
         ctx.mark_non_differentiable(*outs)
         if diag["time"] is not None:
             ctx.mark_non_differentiable(diag["time"])
-        return (loss,) + outs + ((diag["time"],) if diag["time"] is not None else ())
+        ctx.mark_non_differentiable(diag["loss"])
+        # (the per-graph losses last: TrainLoop's history sums them on the device)
+        return ((loss,) + outs + ((diag["time"],) if diag["time"] is not None else ())
+                + (diag["loss"],))
 
     @staticmethod
     def backward(ctx, g_loss, *unused):
@@ -126,7 +130,31 @@ def loss_function(graph, class_info, pclass=0.1, pfiber=1.0, sharpness=0.5, fina
     noise): None draws one from torch's CPU generator; an int; or a device
     int64 tensor read in-kernel (a captured step then draws fresh noise per
     replay when the tensor is advanced on the device).  ``noiselevel`` is
-    softfloor's (train.py:21, fixed at 0.3 by the reference's call)."""
+    softfloor's (train.py:21, fixed at 0.3 by the reference's call).
+    ``sharpness``: a Python number, or a 0-d float32 device tensor read
+    in-kernel (the reference anneals it every epoch, train.py:137: a captured
+    step then follows the tensor); softfloor's coefficients are made from it on
+    the device, once per call, in double rounded once to float.  A float32
+    device tensor of 4 elements is taken as those coefficients already made
+    (``TrainLoop`` fills them in the launch that advances the schedule)."""
+    d, ci, outs = _loss_apply(graph, class_info, pclass, pfiber, sharpness, finaloutput, gnn, seed,
+                              noiselevel)
+    loss, utils_g, n_prime, fiber_time, variance = outs[:5]
+    if not finaloutput:
+        return loss, utils_g.sum() if d.G > 1 else utils_g[0]
+    time = outs[5]
+    Ni = ci[1] / config.NFIELDS
+    comp = (n_prime / Ni).detach().cpu().numpy()
+    fibers = fiber_time.detach().cpu().numpy()
+    utils = utils_g.sum() if d.G > 1 else utils_g[0]
+    var = variance.sum() if d.G > 1 else variance[0]
+    return loss, utils, comp, n_prime, fibers, time, var
+
+
+def _loss_apply(graph, class_info, pclass, pfiber, sharpness, want_time, gnn, seed, noiselevel):
+    """loss_function's checks and the fused op: -> (dims, class_info [2, NT],
+    (loss, utils [G], n_prime, fiber_time, variance [G], time [E] if
+    ``want_time``, loss [G])), every one a device tensor."""
     pf = graph.__dict__.get("_pf")
     if pf is None or graph.__dict__.get("_pf_replaced"):
         raise NotImplementedError("loss_function needs the BipartiteData returned by "
@@ -157,18 +185,18 @@ def loss_function(graph, class_info, pclass=0.1, pfiber=1.0, sharpness=0.5, fina
         seed = draw_seed()
     elif not isinstance(seed, torch.Tensor):
         seed = int(seed)
-    outs = _LossFn.apply(token, model.encoder_s[0].weight, model, d, ectx, xe3, ci, float(sharpness),
-                         seed, float(pclass), float(pfiber), bool(finaloutput), float(noiselevel))
-    loss, utils_g, n_prime, fiber_time, variance = outs[:5]
-    if not finaloutput:
-        return loss, utils_g.sum() if d.G > 1 else utils_g[0]
-    time = outs[5]
-    Ni = ci[1] / config.NFIELDS
-    comp = (n_prime / Ni).detach().cpu().numpy()
-    fibers = fiber_time.detach().cpu().numpy()
-    utils = utils_g.sum() if d.G > 1 else utils_g[0]
-    var = variance.sum() if d.G > 1 else variance[0]
-    return loss, utils, comp, n_prime, fibers, time, var
+    if isinstance(sharpness, torch.Tensor):
+        if (sharpness.device.type != config.device.type or not sharpness.is_floating_point()
+                or sharpness.numel() not in (1, 4)):
+            raise ValueError("a tensor sharpness must be one float on the device (or softfloor's "
+                             f"4 coefficients); got {tuple(sharpness.shape)} {sharpness.dtype} on "
+                             f"{sharpness.device}")
+        sharpness = sharpness.detach()
+    else:
+        sharpness = float(sharpness)
+    outs = _LossFn.apply(token, model.encoder_s[0].weight, model, d, ectx, xe3, ci, sharpness,
+                         seed, float(pclass), float(pfiber), bool(want_time), float(noiselevel))
+    return d, ci, outs
 
 
 # ---------------------------------------------------------------- training
@@ -185,6 +213,270 @@ def complete_graph(class_info, nfibers, fdim, lo=2.0, hi=10.0):
     return BipartiteData(edge_index=edge_index, x_s=x_s, x_t=class_info, x_e=x_e, x_u=x_u)
 
 
+class TrainLoop:
+    """train.py:133-165 with nothing of an epoch on the host: the annealed
+    sharpness (train.py:137), the history rows (train.py:143-145), the
+    best-tracking (train.py:146-152) and the checkpoint of the best state
+    (train.py:154-158) are device values and small launches around the forward,
+    loss, backward and Adam, so the whole epoch is one HIP-graph replay.
+
+    Launch order of an epoch: ``train_advance`` (epoch += 1, seed += 1, the
+    sharpness and softfloor's coefficients) | zero_grad, GNN forward, loss
+    forward + finalize | ``train_record`` (history rows, improved?) | backward |
+    Adam | ``copy_if`` (improved: parameters, Adam state, BatchNorm buffers,
+    time, fiber_time, completion -> the best snapshot).  As in the reference the
+    best time / fiber_time / completion are those of the forward before the
+    update and the checkpointed weights those after ``optimizer.step()``.
+
+    ``run(n)`` does n epochs: the first eagerly (layout caches, workspace, Adam
+    state), the second on a side stream, then it captures the step and replays
+    it; ``capture=False`` issues the same launches eagerly.  The host only
+    counts epochs.  ``history()``, ``best()``, ``checkpoint()`` and
+    ``best_checkpoint()`` read the device state (one sync each, at call time).
+
+    One divergence from the reference: it rewrites the checkpoint file on every
+    improvement; here the best state stays on the device until asked for.
+    ``seed``: softfloor's noise seed before the first epoch (epoch e draws with
+    seed + e - start_epoch + 1); None draws one from torch's CPU generator."""
+
+    def __init__(self, gnn, optimizer, graph, class_info, nepochs, sharps, min_sharp, pclass,
+                 pfiber, seed=None, start_epoch=0, capture=True, record_completions=True):
+        from .optim import FusedAdam
+        dist = torch.distributed
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise NotImplementedError(
+                "TrainLoop is single-process: a process group of "
+                f"{dist.get_world_size()} ranks is active (collectives inside the capture "
+                "and per-rank utilities are not supported)")
+        if not isinstance(optimizer, FusedAdam) or not all(
+                g.get("capturable", False) for g in optimizer.param_groups):
+            raise ValueError("TrainLoop needs pfsgnn.FusedAdam(capturable=True): the step count "
+                             "must live on the device")
+        nepochs, start_epoch = int(nepochs), int(start_epoch)
+        if nepochs <= 0 or not 0 <= start_epoch <= nepochs:
+            raise ValueError(f"need nepochs > 0 and 0 <= start_epoch <= nepochs; got {nepochs}, "
+                             f"{start_epoch}")
+        self.gnn, self.optimizer, self.graph = gnn, optimizer, graph
+        self.nepochs, self.start_epoch, self.epoch = nepochs, start_epoch, start_epoch
+        self.sharps = (sharps[0], sharps[1])
+        self.min_sharp, self.pclass, self.pfiber = float(min_sharp), float(pclass), float(pfiber)
+        self.capture = bool(capture)
+        be = self._be = backend()
+        dev, fdt = config.device, be.dtype
+        self.class_info = class_info.to(device=dev)
+        NT, NS = self.class_info.shape[0], graph.x_s.shape[0]
+        E, G = graph.edge_index.shape[1], graph.x_u.shape[0]
+        if NT % G:
+            raise ValueError(f"class_info has {NT} rows for {G} graphs")
+
+        def buf(*shape, dtype=fdt, fill=0):
+            return torch.full(shape, fill, dtype=dtype, device=dev)
+
+        # the schedule (the epoch counter holds the epoch last run)
+        self._epoch = buf(1, dtype=torch.int64, fill=start_epoch - 1)
+        self._seed = buf(dtype=torch.int64, fill=draw_seed() if seed is None else int(seed))
+        self._sharp, self._sf = buf(), buf(4)
+        # the history (train.py:114-122) and the best state (train.py:117-121)
+        self._losses, self._objective, self._variances = buf(nepochs), buf(nepochs), buf(nepochs)
+        self._completions = buf(NT, nepochs) if record_completions else None
+        self._comp, self._improved = buf(NT), buf(1, dtype=torch.int32)
+        self._best_utility, self._best_loss = buf(1), buf(1)
+        self._best_epoch = buf(1, dtype=torch.int64, fill=-1)
+        self._best_time, self._best_fiber_time, self._best_completion = buf(E), buf(NS), buf(NT)
+        self._jobs = self._snap = None
+        self._graph, self._warm = None, 0
+
+    # ------------------------------------------------------------ the three ops
+    # (the backend's launches; torch restatements when it has none, for a CPU
+    # emulation of the op set)
+    def _advance(self):
+        be = self._be
+        if hasattr(be, "train_advance"):
+            be.train_advance(self._epoch, self._seed, self.sharps[0], self.sharps[1], self.nepochs,
+                             self._sharp, self._sf)
+            return self._sf
+        self._epoch += 1
+        self._seed += 1
+        e = int(self._epoch)
+        self._sharp.fill_(self.sharps[0] + (self.sharps[1] - self.sharps[0]) * e / self.nepochs)
+        return self._sharp
+
+    def _record(self, d, ci, loss_g, utils_g, variance_g, n_prime):
+        be = self._be
+        if hasattr(be, "train_record"):
+            be.train_record(d, self.nepochs, self._epoch, self._sharp, loss_g, utils_g, variance_g,
+                            n_prime, ci, float(config.NFIELDS), self.min_sharp, self._losses,
+                            self._objective, self._variances, self._completions, self._comp,
+                            self._improved, self._best_utility, self._best_loss, self._best_epoch)
+            return
+        e = int(self._epoch)
+        loss_g, utils_g, variance_g, n_prime = (t.detach() for t in (loss_g, utils_g, variance_g,
+                                                                     n_prime))
+        loss, util, var = loss_g[0], utils_g[0], variance_g[0]
+        for g in range(1, d.G):
+            loss, util, var = loss + loss_g[g], util + utils_g[g], var + variance_g[g]
+        self._comp.copy_(n_prime / (ci[1] / config.NFIELDS))
+        if 0 <= e < self.nepochs:
+            self._losses[e], self._objective[e], self._variances[e] = loss, util, var
+            if self._completions is not None:
+                self._completions[:, e] = self._comp
+        improved = bool(util > self._best_utility[0]) and bool(self._sharp > self.min_sharp)
+        self._improved.fill_(int(improved))
+        if improved:
+            self._best_utility[0], self._best_loss[0], self._best_epoch[0] = util, loss, e
+
+    def _copy_if(self, time, fiber_time):
+        be = self._be
+        extra = [(time, self._best_time), (fiber_time, self._best_fiber_time)]
+        if self._jobs is None:
+            self._build_snapshot()
+        if hasattr(be, "copy_if"):
+            be.copy_if(self._improved, self._jobs, extra)
+        elif int(self._improved):
+            for s, t in self._jobs + extra:
+                t.copy_(s.detach())
+
+    def _build_snapshot(self):
+        """The best state's buffers and the fixed part of the copy list (after
+        the first step: Adam's flat moments and the counters' flat buffer exist)."""
+        gnn, opt = self.gnn, self.optimizer
+        flat = getattr(gnn, "_pf_flat", None)
+        if flat is None:
+            raise ValueError("TrainLoop needs a pfsgnn.GNN (its parameters in one flat buffer)")
+        src = {"flat": flat}
+        for gi, group in enumerate(opt.param_groups):
+            if gi not in opt._flat:
+                raise ValueError("TrainLoop needs FusedAdam's one-launch update: its parameters "
+                                 "and gradients as views of the model's flat buffers")
+            src[f"m{gi}"], src[f"v{gi}"] = opt._flat[gi]
+            src[f"step{gi}"] = opt.state[group["params"][0]]["step"]
+        for name, b in gnn.named_buffers():
+            src["buf:" + name] = b
+        src["comp"] = self._comp
+        self._snap = {k: torch.zeros_like(v) for k, v in src.items()}
+        self._snap["comp"] = self._best_completion
+        pairs = [(src[k].detach(), self._snap[k]) for k in src]
+        self._jobs = self._be.copy_jobs(pairs) if hasattr(self._be, "copy_jobs") else pairs
+
+    # ------------------------------------------------------------ an epoch
+    def _step(self):
+        sharp = self._advance()
+        self.gnn.zero_grad()
+        out = self.gnn(self.graph)
+        # (not finaloutput=True: that form copies its diagnostics to the host)
+        d, ci, outs = _loss_apply(out, self.class_info, self.pclass, self.pfiber, sharp, True, None,
+                                  self._seed, 0.3)
+        loss, utils_g, n_prime, fiber_time, variance_g, time, loss_g = outs
+        self._record(d, ci, loss_g, utils_g, variance_g, n_prime)
+        loss.backward()
+        self.optimizer.step()
+        self._copy_if(time, fiber_time)
+
+    def run(self, n):
+        """n more epochs.  Refuses to pass ``nepochs`` (the history has that many
+        rows, and the schedule ends there)."""
+        n = int(n)
+        if n < 0 or self.epoch + n > self.nepochs:
+            raise ValueError(f"run({n}) from epoch {self.epoch} would pass nepochs = {self.nepochs}")
+        for _ in range(n):
+            if not self.capture:
+                self._step()
+            elif self._graph is not None:
+                self._graph.replay()
+            elif self._warm == 0:
+                self._step()
+                self._warm = 1
+            else:
+                torch.cuda.synchronize()
+                side = torch.cuda.Stream()
+                side.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(side):
+                    self._step()
+                torch.cuda.current_stream().wait_stream(side)
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):     # a host sync inside the step would raise here
+                    self._step()
+                self._graph = g
+                # the capture baked in the addresses of this batch's cached layout
+                # and canonical edge tensor (gnn._LAYOUT_CACHE / _EDGE_CACHE, keyed
+                # by the batch's edge_index and x_e): hold those two entries, so
+                # that an eviction by other batches of the process cannot free
+                # memory the replays read
+                self._pinned = [c.d.get(id(t)) for c, t in
+                                ((_gnn._LAYOUT_CACHE, self.graph.edge_index),
+                                 (_gnn._EDGE_CACHE, self.graph.x_e))]
+            self.epoch += 1
+        return self
+
+    # ------------------------------------------------------------ reading back
+    def sharpness(self):
+        """The sharpness of the epoch last run (host float; one sync)."""
+        return float(self._sharp)
+
+    def history(self):
+        """train.py:114-122's arrays up to the current epoch (rows before
+        ``start_epoch`` are 0): losses, objective, variances [epoch] and
+        completions [NT, epoch] (None without ``record_completions``)."""
+        k = self.epoch
+        bufs = dict(losses=self._losses[:k], objective=self._objective[:k],
+                    variances=self._variances[:k],
+                    completions=None if self._completions is None else self._completions[:, :k])
+        return {n: None if t is None else t.cpu().numpy() for n, t in bufs.items()}
+
+    def best(self):
+        """train.py:117-121, 148-152: loss, utility, epoch (-1: no epoch has
+        qualified) and the time [E], fiber_time [NS], completion [NT] of that epoch."""
+        return dict(loss=float(self._best_loss), utility=float(self._best_utility),
+                    epoch=int(self._best_epoch), time=self._best_time.cpu().numpy(),
+                    fiber_time=self._best_fiber_time.cpu().numpy(),
+                    completion=self._best_completion.cpu().numpy())
+
+    def _optim_state(self, tensors):
+        """optimizer.state_dict() with its state tensors replaced by
+        ``tensors(gi) -> (m flat, v flat, step)``, cloned."""
+        from .optim import _flat_base
+        sd = self.optimizer.state_dict()
+        state, i = {}, 0
+        for gi, group in enumerate(self.optimizer.param_groups):
+            m, v, step = tensors(gi)
+            _, offs = _flat_base([p.detach() for p in group["params"]])
+            for p, off in zip(group["params"], offs):
+                state[i] = {"step": step.clone(), "exp_avg": m[off:off + p.numel()].view(p.shape).clone(),
+                            "exp_avg_sq": v[off:off + p.numel()].view(p.shape).clone()}
+                i += 1
+        return {"state": state, "param_groups": sd["param_groups"]}
+
+    def checkpoint(self, epoch=None):
+        """train.py:161-165's dict for the current state; ``epoch`` defaults to
+        the epoch last run, so that a resume (train.py:132) continues with the next."""
+        if self._jobs is None:    # before the first step: the optimizer's own (empty) state
+            optim_state = self.optimizer.state_dict()
+        else:
+            opt = self.optimizer
+            optim_state = self._optim_state(
+                lambda gi: opt._flat[gi] + (opt.state[opt.param_groups[gi]["params"][0]]["step"],))
+        model_state = type(self.gnn.state_dict())(
+            (k, v.detach().clone()) for k, v in self.gnn.state_dict().items())
+        return {"epoch": self.epoch - 1 if epoch is None else int(epoch),
+                "model_state": model_state, "optim_state": optim_state}
+
+    def best_checkpoint(self):
+        """train.py:154-158's dict of the best epoch (weights and optimizer state
+        after that epoch's update); None when no epoch has qualified."""
+        e = int(self._best_epoch)
+        if e < 0 or self._snap is None:
+            return None
+        snap, gnn = self._snap, self.gnn
+        pslice = {n: snap["flat"][off:off + cnt].view(p.shape)
+                  for (n, p), (off, cnt) in zip(gnn.named_parameters(), gnn._pf_off)}
+        sd = gnn.state_dict()
+        model_state = type(sd)(
+            (k, (pslice[k] if k in pslice else snap["buf:" + k]).clone()) for k in sd)
+        optim_state = self._optim_state(
+            lambda gi: (snap[f"m{gi}"], snap[f"v{gi}"], snap[f"step{gi}"]))
+        return {"epoch": e, "model_state": model_state, "optim_state": optim_state}
+
+
 def main(argv=None):
     """train.py:82-165 (training + checkpointing; the plotting of train.py:168-305
     is not part of the hot path and is skipped)."""
@@ -197,30 +489,27 @@ def main(argv=None):
     graph = complete_graph(class_info, NF, config.Fdim)
     gnn = GNN(Fdim=config.Fdim, B=3, F_s=1, F_t=class_info.shape[1], T=NC).to(config.device)
     gnn.train()
-    optimizer = FusedAdam(gnn.parameters(), lr=config.lr)
+    optimizer = FusedAdam(gnn.parameters(), lr=config.lr, capturable=True)
     nepochs = config.nepochs
     start_epoch = 0
     if argv:
         ck = torch.load(argv[0], map_location=config.device, weights_only=True)
         gnn.load_state_dict(ck["model_state"])
         optimizer.load_state_dict(ck["optim_state"])
-        start_epoch = ck["epoch"] + 1
-    best_utility = 0.0
-    for epoch in range(start_epoch, nepochs):
-        gnn.zero_grad()
-        graph_ = gnn(graph)
-        sharp = config.sharps[0] + (config.sharps[1] - config.sharps[0]) * epoch / nepochs
-        loss, utility, comp, _, fiber_time, time, variance = loss_function(
-            graph_, class_info, pclass=config.pclass, pfiber=config.pfiber, sharpness=sharp,
-            finaloutput=True)
-        loss.backward()
-        optimizer.step()
-        if float(utility) > best_utility and sharp > config.min_sharp:
-            best_utility = float(utility)
-            torch.save({"epoch": epoch, "model_state": gnn.state_dict(),
-                        "optim_state": optimizer.state_dict()}, config.checkpoint_path + ID + ".pth")
-    torch.save({"epoch": nepochs, "model_state": gnn.state_dict(),
-                "optim_state": optimizer.state_dict()}, config.checkpoint_path + ID + ".pth")
+        start_epoch = min(ck["epoch"] + 1, nepochs)   # (a final checkpoint: nothing left to run)
+    # the whole epoch (schedule, forward, loss, history, backward, Adam, best
+    # snapshot) as one graph replay; PFSGNN_TRAIN_CAPTURE=0: the same launches eagerly
+    loop = TrainLoop(gnn, optimizer, graph, class_info, nepochs, config.sharps, config.min_sharp,
+                     config.pclass, config.pfiber, start_epoch=start_epoch,
+                     capture=os.environ.get("PFSGNN_TRAIN_CAPTURE", "1") != "0")
+    loop.run(max(0, nepochs - start_epoch))
+    # train.py:161-165, and the best state beside it (the reference rewrites the
+    # one file on every improvement and then overwrites it with the final state)
+    torch.save(loop.checkpoint(epoch=nepochs), config.checkpoint_path + ID + ".pth")
+    best = loop.best_checkpoint()
+    if best is not None:
+        torch.save(best, config.checkpoint_path + ID + "_best.pth")
+    return loop
 
 
 if __name__ == "__main__":
