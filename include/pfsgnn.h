@@ -514,7 +514,7 @@ int pfsgnn_bn2_bwd_coef(const float* Sg, const float* Sgx, const float* mu1, con
                         const float* gamma, int C, long long n, float eps, float* alpha,
                         float* gam0, float* gam1, float* dgamma, float* dbeta, void* stream);
 /* the same from per-block partials part [nparts][2C] (sum g in 0..C, sum
- * g*xhat in C..2C; pfsgnn_loss_bwd_bn's bn_part), summed in a fixed order */
+ * g*xhat in C..2C; pfsgnn_loss_bwd's bn_part), summed in a fixed order */
 int pfsgnn_bn2_bwd_coef_part(const float* part, int nparts, int C, const float* gamma,
                              const float* mu1, const float* var1, long long n, float eps,
                              float* alpha, float* gam0, float* gam1, float* dgamma, float* dbeta,
@@ -615,7 +615,7 @@ typedef struct {
  * the CU's 160 KB (e.g. 124 at Fdim 16 on the default path), and at most 128.
  * 0: no sliced kernels for this (F, path) -- the bf16 edge-state paths and
  * Fdims other than 8 / 10 / 16.  A batch above the limit runs the composed
- * general-graph ops (pfsgnn.sparse); the edge ops and pfsgnn_sl_loss_* refuse it.
+ * general-graph ops (pfsgnn.sparse); the edge ops and the loss ops refuse it.
  * (Host-side query; it reads the kernels' attributes from the HIP runtime.) */
 int pfsgnn_sliced_max_nc(int F, int* nc);
 size_t pfsgnn_sliced_plan_ws_bytes(int G, int NF);
@@ -820,51 +820,29 @@ int pfsgnn_edge_mlp_bwd(const pfsgnn_edge_mlp_bwd_args* a, void* ws, size_t ws_b
  * row 1 = N_i).  Noise uniforms come from a counter-based hash of
  * (seed, edge); seed_dev (optional, device uint64) overrides `seed` so a
  * captured graph draws fresh noise per replay.  tt (optional) = per-edge
- * allocated time [E] in train.py's fiber-major order. */
-int pfsgnn_loss_fwd(int G, int NF, int NC, int F, const float* y, const float* sc,
-                    const float* sh, const float* Wd1, const float* bd1, const float* Wd2,
-                    const float* bd2, const float* ci, float scale, float sharpness,
-                    float noiselevel, unsigned long long seed,
-                    const unsigned long long* seed_dev, float* n_prime,
-                    float* fiber_time, float* tmean, float* tvar, float* tt,
-                    void* ws, size_t ws_bytes, void* stream);
-int pfsgnn_loss_finalize(int G, int NF, int NC, const float* n_prime, const float* fiber_time,
-                         const float* tvar, const float* ci, float pclass, float pfiber,
-                         float total_time, float nfields, float wutils, float wvar,
-                         float* loss, float* utils, float* variance, float* Gn, float* Gf,
-                         float* Gv, void* stream);
-/* gscale: device scalar (upstream d loss), NULL = 1. gxe = d loss / d xe_final */
-int pfsgnn_loss_bwd(int G, int NF, int NC, int F, const float* y, const float* sc,
-                    const float* sh, const float* Wd1, const float* bd1, const float* Wd2,
-                    const float* bd2, const float* ci, float scale, float sharpness,
-                    float noiselevel, unsigned long long seed,
-                    const unsigned long long* seed_dev, const float* Gn,
-                    const float* Gf, const float* Gv, const float* tmean, const float* gscale,
-                    float* dWd1, float* dbd1, float* dWd2, float* dbd2, float* gxe,
-                    void* ws, size_t ws_bytes, void* stream);
-/* the same, also writing the final EdgeModel BatchNorm's backward sums of gxe
- * (gnn.py:101, the last block's; train.py's objective reads nothing else of
- * it): bn_part [pfsgnn_loss_bn_parts(G, NF, NC)][2F] per-block partials of
- * sum gxe and sum gxe * (y - bn_mu1) * bn_inv1, for pfsgnn_bn2_bwd_coef_part --
- * in place of a pass that reads gxe and y back (pfsgnn_edge_bn_grad_sums) */
-int pfsgnn_loss_bn_parts(int G, int NF, int NC);
-int pfsgnn_loss_bwd_bn(int G, int NF, int NC, int F, const float* y, const float* sc,
-                       const float* sh, const float* Wd1, const float* bd1, const float* Wd2,
-                       const float* bd2, const float* ci, float scale, float sharpness,
-                       float noiselevel, unsigned long long seed,
-                       const unsigned long long* seed_dev, const float* Gn, const float* Gf,
-                       const float* Gv, const float* tmean, const float* gscale, float* dWd1,
-                       float* dbd1, float* dWd2, float* dbd2, float* gxe, const float* bn_mu1,
-                       const float* bn_inv1, float* bn_part, void* ws, size_t ws_bytes,
-                       void* stream);
-
-/* The objective on a SLICED GENERAL batch (pfsgnn_sliced_t; pfsgnn_sl_loss.hip):
- * the three ops above with the layout and pos_user [EP] (pfsgnn_sliced_fill:
- * the caller's edge at each position, -1 at padding) in front of the same
- * arguments.  Replaces train.py:36-71 and decoder_e / edge_prediction
- * (gnn.py:307-312) for a batch whose fibers reach only some classes.
+ * allocated time [E] in train.py's fiber-major order.
  *
- * train.py indexes edges by position (train.py:40, :67), which only means
+ * The forward and the backward take ONE argument struct, complete and sliced
+ * batches alike.  Optional groups are left NULL / 0:
+ *   sl + pos_user   a sliced general batch (both, or neither: complete graphs);
+ *   seed_dev        a device seed overriding `seed`;
+ *   sf_dev          a device softfloor record overriding `sharpness` (below);
+ *   tt              the per-edge time;
+ *   gscale          device scalar (upstream d loss), NULL = 1;
+ *   bn_mu1, bn_inv1, bn_part   the final BatchNorm's sums (below; all three;
+ *                   complete graphs only).
+ * pfsgnn_loss_fwd reads the inputs and writes n_prime, fiber_time, tmean, tvar
+ * (and tt); pfsgnn_loss_bwd reads tmean, Gn, Gf, Gv (and gscale) and writes
+ * dWd1, dbd1, dWd2, dbd2, gxe = d loss / d xe_final (and bn_part).  Fields of
+ * the other direction are ignored.  Every argument check runs before the first
+ * launch.  Workspace: pfsgnn_workspace_bytes.
+ *
+ * sl + pos_user -- the objective on a SLICED GENERAL batch (pfsgnn_sliced_t;
+ * pfsgnn_sl_loss.hip): sl is the layout, pos_user [sl->EP] (pfsgnn_sliced_fill)
+ * the caller's edge at each position, -1 at padding.  Replaces train.py:36-71
+ * and decoder_e / edge_prediction (gnn.py:307-312) for a batch whose fibers
+ * reach only some classes.
+ *   train.py indexes edges by position (train.py:40, :67), which only means
  * something on the complete fiber-major graph; here every edge e = (src_e,
  * tgt_e) is indexed by edge_index:
  *   time_e = softplus(decoder_e(x_e)) * scale   (scale = TOTAL_TIME / NC, NC the
@@ -880,64 +858,35 @@ int pfsgnn_loss_bwd_bn(int G, int NF, int NC, int F, const float* y, const float
  *   edges with tgt_e = c.  A class with deg(c) < 2 contributes 0 and gets no
  *   variance gradient -- the one divergence from the reference, whose
  *   torch.var would give NaN there;
- *   class and fiber penalties and the sum over graphs as pfsgnn_loss_finalize.
+ *   class and fiber penalties and the sum over graphs as on complete graphs.
  * softfloor's uniform of edge e is the counter-based hash of (seed, e) with e
  * the CALLER's edge position (pos_user) -- the dense kernels' counter,
  * independent of the sliced layout.  On a complete fiber-major batch the
- * values equal the dense ops'.
- *
- * Shapes: y, gxe [F][sl->EP] in slot order (gxe: every position written, 0 at
- * padding); tt (optional) [sl->E] in the caller's edge order; n_prime, tmean,
- * Gn, Gv [G*NC]; fiber_time, Gf [G*NF]; tvar [2][G*NC]: row 0 the class
- * variances, row 1 the class edge counts deg(c) of the reduction (read by
- * pfsgnn_sl_loss_finalize for the variance gradient).  Workspace:
- * pfsgnn_workspace_bytes.  No host synchronisation, no allocation, no atomics:
- * capturable and bitwise reproducible.  Refused with an error text before any
- * launch: Fdim outside 8 / 10 / 16, NC above pfsgnn_sliced_max_nc (including
- * edge paths without sliced kernels). */
-int pfsgnn_sl_loss_fwd(const pfsgnn_sliced_t* sl, const int* pos_user, int G, int NF, int NC,
-                       int F, const float* y, const float* sc, const float* sh, const float* Wd1,
-                       const float* bd1, const float* Wd2, const float* bd2, const float* ci,
-                       float scale, float sharpness, float noiselevel, unsigned long long seed,
-                       const unsigned long long* seed_dev, float* n_prime, float* fiber_time,
-                       float* tmean, float* tvar, float* tt, void* ws, size_t ws_bytes,
-                       void* stream);
-int pfsgnn_sl_loss_finalize(const pfsgnn_sliced_t* sl, const int* pos_user, int G, int NF, int NC,
-                            const float* n_prime, const float* fiber_time, const float* tvar,
-                            const float* ci, float pclass, float pfiber, float total_time,
-                            float nfields, float wutils, float wvar, float* loss, float* utils,
-                            float* variance, float* Gn, float* Gf, float* Gv, void* stream);
-/* (the final EdgeModel BatchNorm's backward sums are not fused here: a sliced
- * batch takes pfsgnn_rows_bn_sums over gxe and y) */
-int pfsgnn_sl_loss_bwd(const pfsgnn_sliced_t* sl, const int* pos_user, int G, int NF, int NC,
-                       int F, const float* y, const float* sc, const float* sh, const float* Wd1,
-                       const float* bd1, const float* Wd2, const float* bd2, const float* ci,
-                       float scale, float sharpness, float noiselevel, unsigned long long seed,
-                       const unsigned long long* seed_dev, const float* Gn, const float* Gf,
-                       const float* Gv, const float* tmean, const float* gscale, float* dWd1,
-                       float* dbd1, float* dWd2, float* dbd2, float* gxe, void* ws,
-                       size_t ws_bytes, void* stream);
-
-/* The loss forward and backward behind ONE argument struct, complete and sliced
- * batches alike; the positional entry points above are wrappers over these two
- * and give the same bits.  Optional groups are left NULL / 0:
- *   sl + pos_user   a sliced general batch (both, or neither: complete graphs);
- *   seed_dev        a device seed overriding `seed`;
- *   sf_dev          a device softfloor record overriding `sharpness` (below);
- *   tt              the per-edge time;
- *   bn_mu1, bn_inv1, bn_part   pfsgnn_loss_bwd_bn's sums (all three; complete
- *                   graphs only).
- * pfsgnn_loss_fwd_ex reads the inputs and writes n_prime, fiber_time, tmean,
- * tvar (and tt); pfsgnn_loss_bwd_ex reads tmean, Gn, Gf, Gv (and gscale) and
- * writes dWd1, dbd1, dWd2, dbd2, gxe (and bn_part).  Fields of the other
- * direction are ignored.  Every argument check runs before the first launch.
+ * values equal the dense form's.
+ *   Shapes with sl: y, gxe [F][sl->EP] in slot order (gxe: every position
+ * written, 0 at padding); tt (optional) [sl->E] in the caller's edge order;
+ * n_prime, tmean, Gn, Gv [G*NC]; fiber_time, Gf [G*NF]; tvar [2][G*NC]: row 0
+ * the class variances, row 1 the class edge counts deg(c) of the reduction
+ * (read by pfsgnn_loss_finalize for the variance gradient; without sl tvar is
+ * [G*NC]).  No host synchronisation, no allocation, no atomics: capturable and
+ * bitwise reproducible.  Refused with an error text before any launch: Fdim
+ * outside 8 / 10 / 16, NC above pfsgnn_sliced_max_nc (including edge paths
+ * without sliced kernels), sl without pos_user or the reverse, sl with bn_part.
  *
  * sf_dev: the reference anneals softfloor's sharpness every epoch
  * (train.py:137, read at train.py:21-27); a captured step therefore reads it
  * from the device.  sf_dev points at 4 floats (16-byte aligned), r =
  * exp(-1/sharpness) (0 when sharpness == 0, train.py:26), atan(r / (1 - r)),
  * 2 pi, 1 / pi, filled by pfsgnn_softfloor_record or pfsgnn_train_advance from
- * a device float: r and the arctangent in double, rounded once to float. */
+ * a device float: r and the arctangent in double, rounded once to float.
+ *
+ * bn_mu1, bn_inv1, bn_part: the backward also writes the final EdgeModel
+ * BatchNorm's backward sums of gxe (gnn.py:101, the last block's; train.py's
+ * objective reads nothing else of it): bn_part [pfsgnn_loss_bn_parts(G, NF,
+ * NC)][2F] per-block partials of sum gxe and sum gxe * (y - bn_mu1) * bn_inv1,
+ * for pfsgnn_bn2_bwd_coef_part -- in place of a pass that reads gxe and y back
+ * (pfsgnn_edge_bn_grad_sums).  Not fused on a sliced batch, which takes
+ * pfsgnn_rows_bn_sums over gxe and y. */
 typedef struct pfsgnn_loss_args {
   int G, NF, NC, F;
   const pfsgnn_sliced_t* sl;
@@ -955,8 +904,17 @@ typedef struct pfsgnn_loss_args {
 } pfsgnn_loss_args;
 /* sizeof(pfsgnn_loss_args), for bindings to check their struct layout */
 size_t pfsgnn_loss_args_bytes(void);
-int pfsgnn_loss_fwd_ex(const pfsgnn_loss_args* a, void* ws, size_t ws_bytes, void* stream);
-int pfsgnn_loss_bwd_ex(const pfsgnn_loss_args* a, void* ws, size_t ws_bytes, void* stream);
+int pfsgnn_loss_fwd(const pfsgnn_loss_args* a, void* ws, size_t ws_bytes, void* stream);
+int pfsgnn_loss_bwd(const pfsgnn_loss_args* a, void* ws, size_t ws_bytes, void* stream);
+/* between the two: train.py:53-71 per graph and the gradient coefficients Gn,
+ * Gv [G*NC], Gf [G*NF] the backward reads.  sl NULL: tvar [G*NC]; sl set (only
+ * tested for NULL): tvar [2][G*NC] as the sliced forward writes it */
+int pfsgnn_loss_finalize(const pfsgnn_sliced_t* sl, int G, int NF, int NC, const float* n_prime,
+                         const float* fiber_time, const float* tvar, const float* ci,
+                         float pclass, float pfiber, float total_time, float nfields,
+                         float wutils, float wvar, float* loss, float* utils, float* variance,
+                         float* Gn, float* Gf, float* Gv, void* stream);
+int pfsgnn_loss_bn_parts(int G, int NF, int NC);
 /* sf [4] from the device float *sharpness (one thread; train.py:26) */
 int pfsgnn_softfloor_record(const float* sharpness, float* sf, void* stream);
 

@@ -368,10 +368,9 @@ EdgeGeo loss_geo(int G, int NF, int NC) {
 
 
 // The loss ops take one argument struct (pfsgnn_loss_args, include/pfsgnn.h);
-// the positional entry points below fill it and call the same code.  `where`
-// names the entry point the caller used in error texts.
-static int loss_fwd_impl(const char* where, const pfsgnn_loss_args& a, void* ws, size_t ws_bytes,
-                         void* stream) {
+// a->sl selects the sliced general-graph form (pfsgnn_sl_loss.hip).
+static int loss_fwd_dense(const pfsgnn_loss_args& a, void* ws, size_t ws_bytes, void* stream) {
+  const char* where = "pfsgnn_loss_fwd";
   const int G = a.G, NF = a.NF, NC = a.NC, F = a.F;
   if (int rc = check_dims(where, G, NF, NC, F)) return rc;
   PF_REQUIRE(a.y && a.Wd1 && a.bd1 && a.Wd2 && a.bd2 && a.ci && a.n_prime && a.fiber_time &&
@@ -413,45 +412,31 @@ static int loss_args_check(const char* where, const pfsgnn_loss_args* a) {
 
 extern "C" size_t pfsgnn_loss_args_bytes(void) { return sizeof(pfsgnn_loss_args); }
 
-extern "C" int pfsgnn_loss_fwd_ex(const pfsgnn_loss_args* a, void* ws, size_t ws_bytes,
-                                  void* stream) {
-  if (int rc = loss_args_check("pfsgnn_loss_fwd_ex", a)) return rc;
-  if (a->sl) return pf_sl_loss_fwd("pfsgnn_loss_fwd_ex", *a, ws, ws_bytes, stream);
-  return loss_fwd_impl("pfsgnn_loss_fwd_ex", *a, ws, ws_bytes, stream);
+extern "C" int pfsgnn_loss_fwd(const pfsgnn_loss_args* a, void* ws, size_t ws_bytes,
+                               void* stream) {
+  if (int rc = loss_args_check("pfsgnn_loss_fwd", a)) return rc;
+  return a->sl ? pf_sl_loss_fwd(*a, ws, ws_bytes, stream) : loss_fwd_dense(*a, ws, ws_bytes, stream);
 }
 
-extern "C" int pfsgnn_loss_fwd(int G, int NF, int NC, int F, const float* y, const float* sc,
-                               const float* sh, const float* Wd1, const float* bd1,
-                               const float* Wd2, const float* bd2, const float* ci, float scale,
-                               float sharpness, float noiselevel, unsigned long long seed,
-                               const unsigned long long* seed_dev, float* n_prime, float* fiber_time, float* tmean, float* tvar,
-                               float* tt, void* ws, size_t ws_bytes, void* stream) {
-  pfsgnn_loss_args a = {};
-  a.G = G; a.NF = NF; a.NC = NC; a.F = F;
-  a.y = y; a.sc = sc; a.sh = sh; a.Wd1 = Wd1; a.bd1 = bd1; a.Wd2 = Wd2; a.bd2 = bd2; a.ci = ci;
-  a.scale = scale; a.sharpness = sharpness; a.noiselevel = noiselevel;
-  a.seed = seed; a.seed_dev = seed_dev;
-  a.n_prime = n_prime; a.fiber_time = fiber_time; a.tmean = tmean; a.tvar = tvar; a.tt = tt;
-  return loss_fwd_impl("pfsgnn_loss_fwd", a, ws, ws_bytes, stream);
-}
-
-extern "C" int pfsgnn_loss_finalize(int G, int NF, int NC, const float* n_prime,
-                                    const float* fiber_time, const float* tvar, const float* ci,
-                                    float pclass, float pfiber, float total_time, float nfields,
-                                    float wutils, float wvar, float* loss, float* utils,
-                                    float* variance, float* Gn, float* Gf, float* Gv,
-                                    void* stream) {
+extern "C" int pfsgnn_loss_finalize(const pfsgnn_sliced_t* sl, int G, int NF, int NC,
+                                    const float* n_prime, const float* fiber_time,
+                                    const float* tvar, const float* ci, float pclass, float pfiber,
+                                    float total_time, float nfields, float wutils, float wvar,
+                                    float* loss, float* utils, float* variance, float* Gn,
+                                    float* Gf, float* Gv, void* stream) {
   PF_REQUIRE(G > 0 && NF > 1 && NC > 0, "pfsgnn_loss_finalize", "bad dims");
   PF_REQUIRE(n_prime && fiber_time && tvar && ci && loss && utils && variance && Gn && Gf && Gv,
              "pfsgnn_loss_finalize", "null");
-  hipLaunchKernelGGL(k_loss_finalize<false>, dim3(G), dim3(256), 0, as_stream(stream), NF, NC, G * NC,
-                     n_prime, fiber_time, tvar, ci, pclass, pfiber, total_time, nfields, wutils,
-                     wvar, loss, utils, variance, Gn, Gf, Gv);
+  // a sliced batch: tvar is [2][NT], its second row the class edge counts
+  const auto kern = sl ? k_loss_finalize<true> : k_loss_finalize<false>;
+  hipLaunchKernelGGL(kern, dim3(G), dim3(256), 0, as_stream(stream), NF, NC, G * NC, n_prime,
+                     fiber_time, tvar, ci, pclass, pfiber, total_time, nfields, wutils, wvar, loss,
+                     utils, variance, Gn, Gf, Gv);
   return pf::check_launch("pfsgnn_loss_finalize");
 }
 
-static int loss_bwd_impl(const char* where, const pfsgnn_loss_args& a, void* ws, size_t ws_bytes,
-                         void* stream) {
+static int loss_bwd_dense(const pfsgnn_loss_args& a, void* ws, size_t ws_bytes, void* stream) {
+  const char* where = "pfsgnn_loss_bwd";
   const int G = a.G, NF = a.NF, NC = a.NC, F = a.F;
   if (int rc = check_dims(where, G, NF, NC, F)) return rc;
   PF_REQUIRE(a.y && a.Wd1 && a.bd1 && a.Wd2 && a.bd2 && a.ci && a.Gn && a.Gf && a.Gv && a.tmean &&
@@ -481,77 +466,18 @@ static int loss_bwd_impl(const char* where, const pfsgnn_loss_args& a, void* ws,
                                      a.tmean, a.gscale, a.gxe, pW, pV, nullptr, nullptr, nullptr));
   }
   tm_.end(); }
-  {
-    RedDesc rd[4] = {{pW, (int)nb, (size_t)F * (F + 1), F + 1, F, F, a.dWd1, F, 1, 1.f},
-                     {pW + F, (int)nb, (size_t)F * (F + 1), F + 1, F, 1, a.dbd1, 1, 1, 1.f},
-                     {pV, (int)nb, (size_t)(F + 1), F, 1, F, a.dWd2, F, 1, 1.f},
-                     {pV + F, (int)nb, (size_t)(F + 1), 1, 1, 1, a.dbd2, 1, 1, 1.f}};
-    launch_reduce_multi(rd, 4, st);
-  }
+  loss_bwd_reduce(a, pW, pV, nb, st);
   return pf::check_launch(where);
 }
 
-extern "C" int pfsgnn_loss_bwd_ex(const pfsgnn_loss_args* a, void* ws, size_t ws_bytes,
-                                  void* stream) {
-  if (int rc = loss_args_check("pfsgnn_loss_bwd_ex", a)) return rc;
-  if (a->sl) return pf_sl_loss_bwd("pfsgnn_loss_bwd_ex", *a, ws, ws_bytes, stream);
-  return loss_bwd_impl("pfsgnn_loss_bwd_ex", *a, ws, ws_bytes, stream);
-}
-
-static pfsgnn_loss_args loss_bwd_args(int G, int NF, int NC, int F, const float* y, const float* sc,
-                                      const float* sh, const float* Wd1, const float* bd1,
-                                      const float* Wd2, const float* bd2, const float* ci,
-                                      float scale, float sharpness, float noiselevel,
-                                      unsigned long long seed, const unsigned long long* seed_dev,
-                                      const float* Gn, const float* Gf, const float* Gv,
-                                      const float* tmean, const float* gscale, float* dWd1,
-                                      float* dbd1, float* dWd2, float* dbd2, float* gxe) {
-  pfsgnn_loss_args a = {};
-  a.G = G; a.NF = NF; a.NC = NC; a.F = F;
-  a.y = y; a.sc = sc; a.sh = sh; a.Wd1 = Wd1; a.bd1 = bd1; a.Wd2 = Wd2; a.bd2 = bd2; a.ci = ci;
-  a.scale = scale; a.sharpness = sharpness; a.noiselevel = noiselevel;
-  a.seed = seed; a.seed_dev = seed_dev;
-  a.tmean = const_cast<float*>(tmean);   // read only by the backward
-  a.Gn = Gn; a.Gf = Gf; a.Gv = Gv; a.gscale = gscale;
-  a.dWd1 = dWd1; a.dbd1 = dbd1; a.dWd2 = dWd2; a.dbd2 = dbd2; a.gxe = gxe;
-  return a;
-}
-
-extern "C" int pfsgnn_loss_bwd(int G, int NF, int NC, int F, const float* y, const float* sc,
-                               const float* sh, const float* Wd1, const float* bd1,
-                               const float* Wd2, const float* bd2, const float* ci, float scale,
-                               float sharpness, float noiselevel, unsigned long long seed,
-                               const unsigned long long* seed_dev, const float* Gn,
-                               const float* Gf, const float* Gv,
-                               const float* tmean, const float* gscale, float* dWd1, float* dbd1,
-                               float* dWd2, float* dbd2, float* gxe, void* ws, size_t ws_bytes,
+extern "C" int pfsgnn_loss_bwd(const pfsgnn_loss_args* a, void* ws, size_t ws_bytes,
                                void* stream) {
-  const pfsgnn_loss_args a = loss_bwd_args(G, NF, NC, F, y, sc, sh, Wd1, bd1, Wd2, bd2, ci, scale,
-                                           sharpness, noiselevel, seed, seed_dev, Gn, Gf, Gv, tmean,
-                                           gscale, dWd1, dbd1, dWd2, dbd2, gxe);
-  return loss_bwd_impl("pfsgnn_loss_bwd", a, ws, ws_bytes, stream);
+  if (int rc = loss_args_check("pfsgnn_loss_bwd", a)) return rc;
+  return a->sl ? pf_sl_loss_bwd(*a, ws, ws_bytes, stream) : loss_bwd_dense(*a, ws, ws_bytes, stream);
 }
 
 extern "C" int pfsgnn_loss_bn_parts(int G, int NF, int NC) {
   return loss_geo(G, NF, NC).nblocks;
-}
-
-extern "C" int pfsgnn_loss_bwd_bn(int G, int NF, int NC, int F, const float* y, const float* sc,
-                                  const float* sh, const float* Wd1, const float* bd1,
-                                  const float* Wd2, const float* bd2, const float* ci,
-                                  float scale, float sharpness, float noiselevel,
-                                  unsigned long long seed, const unsigned long long* seed_dev,
-                                  const float* Gn, const float* Gf, const float* Gv,
-                                  const float* tmean, const float* gscale, float* dWd1,
-                                  float* dbd1, float* dWd2, float* dbd2, float* gxe,
-                                  const float* bn_mu1, const float* bn_inv1, float* bn_part,
-                                  void* ws, size_t ws_bytes, void* stream) {
-  PF_REQUIRE(bn_mu1 && bn_inv1 && bn_part, "pfsgnn_loss_bwd_bn", "null");
-  pfsgnn_loss_args a = loss_bwd_args(G, NF, NC, F, y, sc, sh, Wd1, bd1, Wd2, bd2, ci, scale,
-                                     sharpness, noiselevel, seed, seed_dev, Gn, Gf, Gv, tmean,
-                                     gscale, dWd1, dbd1, dWd2, dbd2, gxe);
-  a.bn_mu1 = bn_mu1; a.bn_inv1 = bn_inv1; a.bn_part = bn_part;
-  return loss_bwd_impl("pfsgnn_loss_bwd", a, ws, ws_bytes, stream);
 }
 
 extern "C" int pfsgnn_layout_analyze(const int64_t* edge_index, long long E, int G, int NF, int NC,

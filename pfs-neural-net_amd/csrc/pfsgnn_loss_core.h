@@ -5,6 +5,7 @@
 // the LOSS_FAST switch included.
 #pragma once
 #include "pfsgnn_common.h"
+#include "../../include/pfsgnn.h"
 
 #include <cmath>
 
@@ -44,13 +45,21 @@ __device__ __forceinline__ void softfloor_fill(float sharpness, SoftFloor* out) 
 }
 
 // the loss ops on a sliced general batch (pfsgnn_sl_loss.hip), reached from
-// pfsgnn_loss_fwd_ex / _bwd_ex (pfsgnn_loss.hip) when a->sl is set; `where`
-// names the entry point in error texts
-struct pfsgnn_loss_args;
-int pf_sl_loss_fwd(const char* where, const pfsgnn_loss_args& a, void* ws, size_t ws_bytes,
-                   void* stream);
-int pf_sl_loss_bwd(const char* where, const pfsgnn_loss_args& a, void* ws, size_t ws_bytes,
-                   void* stream);
+// pfsgnn_loss_fwd / pfsgnn_loss_bwd (pfsgnn_loss.hip) when a->sl is set
+int pf_sl_loss_fwd(const pfsgnn_loss_args& a, void* ws, size_t ws_bytes, void* stream);
+int pf_sl_loss_bwd(const pfsgnn_loss_args& a, void* ws, size_t ws_bytes, void* stream);
+
+// both backwards' per-block partials pW [nb][F][F+1] (dWd1 | dbd1) and pV
+// [nb][F+1] (dWd2 | dbd2) summed into the decoder's gradients, one launch
+static void loss_bwd_reduce(const pfsgnn_loss_args& a, float* pW, float* pV, size_t nb,
+                            hipStream_t st) {
+  const int F = a.F;
+  const RedDesc rd[4] = {{pW, (int)nb, (size_t)F * (F + 1), F + 1, F, F, a.dWd1, F, 1, 1.f},
+                         {pW + F, (int)nb, (size_t)F * (F + 1), F + 1, F, 1, a.dbd1, 1, 1, 1.f},
+                         {pV, (int)nb, (size_t)(F + 1), F, 1, F, a.dWd2, F, 1, 1.f},
+                         {pV + F, (int)nb, (size_t)(F + 1), 1, 1, 1, a.dbd2, 1, 1, 1.f}};
+  launch_reduce_multi(rd, 4, st);
+}
 
 // decoder_e + softplus*scale + softfloor + clamp (train.py:42-49, gnn.py:307-312).
 // LOSS_FAST: sin / cos of 2 pi x as one sincospi of 2x (the reduction is exact

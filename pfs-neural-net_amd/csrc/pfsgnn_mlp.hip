@@ -2411,7 +2411,7 @@ extern "C" int pfsgnn_target_global_fwd(
 }
 
 // pre_part / pre_n: the BatchNorm sums' per-block partials ([pre_n][32]) made
-// by the producer of dY (pfsgnn_target_bwd_bn); nullptr: k_bn_sums_part here
+// by the producer of dY (pfsgnn_target_bwd's bn_part); nullptr: k_bn_sums_part here
 static int mlp_bwd_impl(const char* where, const float* dY, int N, const float* Yp,
                         const float* mu, const float* var, const float* gamma, float eps,
                         float* dgamma, float* dbeta, const float* Z, const float* W1, int ldw1,

@@ -163,7 +163,7 @@ extern "C" int pfsgnn_timing_query(const char* name, double* total_ms, long long
 }
 
 extern "C" const char* pfsgnn_last_error(void) { return pf::g_err.c_str(); }
-extern "C" const char* pfsgnn_version(void) { return "pfsgnn 0.2 gfx950"; }
+extern "C" const char* pfsgnn_version(void) { return "pfsgnn 0.3 gfx950"; }
 
 // ---------------------------------------------------------------- reduce
 // Partial reductions out[r][c] (+)= scale * sum_b part[b*plen + r*ldp + c],

@@ -338,10 +338,10 @@ int check_sl(const char* where, const pfsgnn_sliced_t* sl, int G, int NF, int NC
 
 }  // namespace
 
-// the sliced forms of the loss ops behind pfsgnn_loss_fwd_ex / _bwd_ex
-// (pfsgnn_loss.hip) and the positional pfsgnn_sl_loss_* entry points below
-int pf_sl_loss_fwd(const char* where, const pfsgnn_loss_args& a, void* ws, size_t ws_bytes,
-                   void* stream) {
+// the sliced forms of the loss ops: pfsgnn_loss_fwd / pfsgnn_loss_bwd
+// (pfsgnn_loss.hip) with a->sl set, sl and pos_user paired there
+int pf_sl_loss_fwd(const pfsgnn_loss_args& a, void* ws, size_t ws_bytes, void* stream) {
+  const char* where = "pfsgnn_loss_fwd";
   const int G = a.G, NF = a.NF, NC = a.NC, F = a.F;
   if (int rc = check_sl(where, a.sl, G, NF, NC, F)) return rc;
   PF_REQUIRE(a.pos_user && a.y && a.Wd1 && a.bd1 && a.Wd2 && a.bd2 && a.ci && a.n_prime &&
@@ -372,42 +372,8 @@ int pf_sl_loss_fwd(const char* where, const pfsgnn_loss_args& a, void* ws, size_
   return pf::check_launch(where);
 }
 
-extern "C" int pfsgnn_sl_loss_fwd(const pfsgnn_sliced_t* sl, const int* pos_user, int G, int NF,
-                                  int NC, int F, const float* y, const float* sc, const float* sh,
-                                  const float* Wd1, const float* bd1, const float* Wd2,
-                                  const float* bd2, const float* ci, float scale, float sharpness,
-                                  float noiselevel, unsigned long long seed,
-                                  const unsigned long long* seed_dev, float* n_prime,
-                                  float* fiber_time, float* tmean, float* tvar, float* tt, void* ws,
-                                  size_t ws_bytes, void* stream) {
-  pfsgnn_loss_args a = {};
-  a.G = G; a.NF = NF; a.NC = NC; a.F = F; a.sl = sl; a.pos_user = pos_user;
-  a.y = y; a.sc = sc; a.sh = sh; a.Wd1 = Wd1; a.bd1 = bd1; a.Wd2 = Wd2; a.bd2 = bd2; a.ci = ci;
-  a.scale = scale; a.sharpness = sharpness; a.noiselevel = noiselevel;
-  a.seed = seed; a.seed_dev = seed_dev;
-  a.n_prime = n_prime; a.fiber_time = fiber_time; a.tmean = tmean; a.tvar = tvar; a.tt = tt;
-  return pf_sl_loss_fwd("pfsgnn_sl_loss_fwd", a, ws, ws_bytes, stream);
-}
-
-extern "C" int pfsgnn_sl_loss_finalize(const pfsgnn_sliced_t* sl, const int* pos_user, int G,
-                                       int NF, int NC, const float* n_prime,
-                                       const float* fiber_time, const float* tvar, const float* ci,
-                                       float pclass, float pfiber, float total_time, float nfields,
-                                       float wutils, float wvar, float* loss, float* utils,
-                                       float* variance, float* Gn, float* Gf, float* Gv,
-                                       void* stream) {
-  (void)pos_user;
-  PF_REQUIRE(sl && G > 0 && NF > 1 && NC > 0, "pfsgnn_sl_loss_finalize", "bad dims");
-  PF_REQUIRE(n_prime && fiber_time && tvar && ci && loss && utils && variance && Gn && Gf && Gv,
-             "pfsgnn_sl_loss_finalize", "null");
-  hipLaunchKernelGGL(k_loss_finalize<true>, dim3(G), dim3(256), 0, as_stream(stream), NF, NC,
-                     G * NC, n_prime, fiber_time, tvar, ci, pclass, pfiber, total_time, nfields,
-                     wutils, wvar, loss, utils, variance, Gn, Gf, Gv);
-  return pf::check_launch("pfsgnn_sl_loss_finalize");
-}
-
-int pf_sl_loss_bwd(const char* where, const pfsgnn_loss_args& a, void* ws, size_t ws_bytes,
-                   void* stream) {
+int pf_sl_loss_bwd(const pfsgnn_loss_args& a, void* ws, size_t ws_bytes, void* stream) {
+  const char* where = "pfsgnn_loss_bwd";
   const int G = a.G, NF = a.NF, NC = a.NC, F = a.F;
   if (int rc = check_sl(where, a.sl, G, NF, NC, F)) return rc;
   PF_REQUIRE(a.pos_user && a.y && a.Wd1 && a.bd1 && a.Wd2 && a.bd2 && a.ci && a.Gn && a.Gf &&
@@ -430,33 +396,6 @@ int pf_sl_loss_bwd(const char* where, const pfsgnn_loss_args& a, void* ws, size_
                                         a.ci, a.scale, sf, sfd, a.noiselevel, key, a.seed_dev, a.Gn,
                                         a.Gf, a.Gv, a.tmean, a.gscale, a.gxe, pW, pV));
   tm_.end(); }
-  {
-    RedDesc rd[4] = {{pW, (int)nb, (size_t)F * (F + 1), F + 1, F, F, a.dWd1, F, 1, 1.f},
-                     {pW + F, (int)nb, (size_t)F * (F + 1), F + 1, F, 1, a.dbd1, 1, 1, 1.f},
-                     {pV, (int)nb, (size_t)(F + 1), F, 1, F, a.dWd2, F, 1, 1.f},
-                     {pV + F, (int)nb, (size_t)(F + 1), 1, 1, 1, a.dbd2, 1, 1, 1.f}};
-    launch_reduce_multi(rd, 4, st);
-  }
+  loss_bwd_reduce(a, pW, pV, nb, st);
   return pf::check_launch(where);
-}
-
-extern "C" int pfsgnn_sl_loss_bwd(const pfsgnn_sliced_t* sl, const int* pos_user, int G, int NF,
-                                  int NC, int F, const float* y, const float* sc, const float* sh,
-                                  const float* Wd1, const float* bd1, const float* Wd2,
-                                  const float* bd2, const float* ci, float scale, float sharpness,
-                                  float noiselevel, unsigned long long seed,
-                                  const unsigned long long* seed_dev, const float* Gn,
-                                  const float* Gf, const float* Gv, const float* tmean,
-                                  const float* gscale, float* dWd1, float* dbd1, float* dWd2,
-                                  float* dbd2, float* gxe, void* ws, size_t ws_bytes,
-                                  void* stream) {
-  pfsgnn_loss_args a = {};
-  a.G = G; a.NF = NF; a.NC = NC; a.F = F; a.sl = sl; a.pos_user = pos_user;
-  a.y = y; a.sc = sc; a.sh = sh; a.Wd1 = Wd1; a.bd1 = bd1; a.Wd2 = Wd2; a.bd2 = bd2; a.ci = ci;
-  a.scale = scale; a.sharpness = sharpness; a.noiselevel = noiselevel;
-  a.seed = seed; a.seed_dev = seed_dev;
-  a.tmean = const_cast<float*>(tmean);   // read only by the backward
-  a.Gn = Gn; a.Gf = Gf; a.Gv = Gv; a.gscale = gscale;
-  a.dWd1 = dWd1; a.dbd1 = dbd1; a.dWd2 = dWd2; a.dbd2 = dbd2; a.gxe = gxe;
-  return pf_sl_loss_bwd("pfsgnn_sl_loss_bwd", a, ws, ws_bytes, stream);
 }

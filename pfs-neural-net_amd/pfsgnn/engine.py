@@ -845,7 +845,7 @@ class Engine:
         """train.py:29-80 on the final edge state ``xe3``.  ``ci`` = class_info
         channel-major [>=2, NT] (row 0 = T_i hours per visit, row 1 = N_i).
         On a sliced general batch (``d.sp.sl``) the backend runs the
-        edge_index-indexed form (include/pfsgnn.h, pfsgnn_sl_loss_fwd): xe3 in
+        edge_index-indexed form (include/pfsgnn.h, pfsgnn_loss_args' sl): xe3 in
         slot order, ``time`` in the caller's edge order.  ``sharpness``: a
         Python number, or a device tensor read in-kernel -- one float32 (its
         softfloor record is made here, once; the backward reuses it) or an

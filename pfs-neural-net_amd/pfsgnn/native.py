@@ -299,13 +299,12 @@ _SIGS = {
     "pfsgnn_tbwd_fold": ([I], I),
     "pfsgnn_msg_bytes": ([I, I, I, I], SZ),
     "pfsgnn_edge_bn_grad_sums": ([I, I, I, I, P, P, P, P, P, P, P, SZ, P], I),
-    "pfsgnn_loss_fwd": ([I, I, I, I, P, P, P, P, P, P, P, P, FL, FL, FL, ULL, P, P, P, P, P, P, P, SZ, P], I),
-    "pfsgnn_loss_finalize": ([I, I, I, P, P, P, P, FL, FL, FL, FL, FL, FL, P, P, P, P, P, P, P], I),
-    "pfsgnn_loss_bwd": ([I, I, I, I, P, P, P, P, P, P, P, P, FL, FL, FL, ULL, P, P, P, P, P, P,
-                         P, P, P, P, P, P, SZ, P], I),
+    "pfsgnn_loss_args_bytes": ([], SZ),
+    "pfsgnn_loss_fwd": ([ctypes.POINTER(LossArgs), P, SZ, P], I),
+    "pfsgnn_loss_finalize": ([SLP, I, I, I, P, P, P, P, FL, FL, FL, FL, FL, FL, P, P, P, P, P, P,
+                              P], I),
+    "pfsgnn_loss_bwd": ([ctypes.POINTER(LossArgs), P, SZ, P], I),
     "pfsgnn_loss_bn_parts": ([I, I, I], I),
-    "pfsgnn_loss_bwd_bn": ([I, I, I, I, P, P, P, P, P, P, P, P, FL, FL, FL, ULL, P, P, P, P, P,
-                            P, P, P, P, P, P, P, P, P, P, SZ, P], I),
     "pfsgnn_layout_analyze": ([P, LL, I, I, I, P, P, P, SZ, P], I),
     "pfsgnn_edges_to_canonical": ([P, I, I, I, I, I, P, P, P], I),
     "pfsgnn_edges_from_canonical": ([P, P, P, I, I, I, I, I, P, I, P, P], I),
@@ -326,9 +325,6 @@ _SIGS = {
     "pfsgnn_edges_from_slots": ([P, P, P, LL, LL, I, P, I, P, P], I),
     "pfsgnn_sl_tmask_bytes": ([SLP, I], SZ),
     "pfsgnn_edge_args_bytes": ([I], SZ),
-    "pfsgnn_loss_args_bytes": ([], SZ),
-    "pfsgnn_loss_fwd_ex": ([ctypes.POINTER(LossArgs), P, SZ, P], I),
-    "pfsgnn_loss_bwd_ex": ([ctypes.POINTER(LossArgs), P, SZ, P], I),
     "pfsgnn_softfloor_record": ([P, P, P], I),
     "pfsgnn_train_advance": ([P, P, ctypes.c_double, ctypes.c_double, LL, P, P, P], I),
     "pfsgnn_train_record_args_bytes": ([], SZ),
@@ -337,12 +333,9 @@ _SIGS = {
 }
 for _op, _cls in EDGE_ARGS.items():
     _SIGS["pfsgnn_" + _op] = ([ctypes.POINTER(_cls), P, SZ, P], I)
-# the objective on a sliced general batch: the layout and pos_user, then the dense op's arguments
-for _op in ("loss_fwd", "loss_finalize", "loss_bwd"):
-    _SIGS["pfsgnn_sl_" + _op] = ([SLP, P] + _SIGS["pfsgnn_" + _op][0], I)
 
 
-ABI_VERSION = "pfsgnn 0.2 gfx950"   # pfsgnn_version() of the library these signatures describe
+ABI_VERSION = "pfsgnn 0.3 gfx950"  # pfsgnn_version() of the library these signatures describe
 
 
 def lib():
@@ -367,11 +360,14 @@ def lib():
             fn = getattr(L, name)
             fn.argtypes = args
             fn.restype = ret
-        for query, cls in (("pfsgnn_loss_args_bytes", LossArgs),
-                           ("pfsgnn_train_record_args_bytes", TrainRecordArgs)):
-            if getattr(L, query)() != ctypes.sizeof(cls):
+        sizes = [("pfsgnn_loss_args_bytes", (), LossArgs),
+                 ("pfsgnn_train_record_args_bytes", (), TrainRecordArgs)]
+        sizes += [("pfsgnn_edge_args_bytes", (op,), cls) for op, cls in enumerate(EDGE_ARGS.values())]
+        for query, qargs, cls in sizes:
+            got, call = getattr(L, query)(*qargs), f"{query}({', '.join(map(str, qargs))})"
+            if got != ctypes.sizeof(cls):
                 raise NativeUnavailable(
-                    f"{_LIB_PATH}: {query}() = {getattr(L, query)()} but this binding's "
+                    f"{_LIB_PATH}: {call} = {got} but this binding's "
                     f"{cls.__name__} has {ctypes.sizeof(cls)} bytes: rebuild the library")
         _lib = L
         path = os.environ.get("PFSGNN_EDGE_PATH")
@@ -1533,20 +1529,12 @@ class HipBackend:
                 "classes per graph than pfsgnn_sliced_max_nc, or a bf16 edge-state path)")
         return d.sp.sl
 
-    @staticmethod
-    def _lcall(op, sl, *args):
-        """pfsgnn_<op>, or pfsgnn_sl_<op>(layout, pos_user, same arguments) on a sliced batch."""
-        if sl is None:
-            _call("pfsgnn_" + op, *args)
-        else:
-            _call("pfsgnn_sl_" + op, sl.ref, sl.pos_user.data_ptr(), *args)
-
     def loss_fwd(self, d, y, sc, sh, Wd1, bd1, Wd2, bd2, ci, scale, sharpness, noiselevel, seed,
                  want_time=False):
         """On a sliced general batch (``d.sp.sl``): y is [F, EP] in slot order,
         tt [E] in the caller's edge order, and tvar is [2, NT] -- the class
         variances and, for loss_finalize, the class edge counts
-        (pfsgnn_sl_loss_fwd)."""
+        (pfsgnn_loss_fwd with sl set)."""
         sl = self._loss_layout(d)
         n_prime, fiber_time = self.empty(d.NT), self.empty(d.NS)
         tmean = self.empty(d.NT)
@@ -1559,7 +1547,7 @@ class HipBackend:
         a.n_prime, a.fiber_time = n_prime.data_ptr(), fiber_time.data_ptr()
         a.tmean, a.tvar, a.tt = tmean.data_ptr(), tvar.data_ptr(), _ptr(tt)
         ws, wsb = self._wsargs(d)
-        _call("pfsgnn_loss_fwd_ex", ctypes.byref(a), ws, wsb, _stream())
+        _call("pfsgnn_loss_fwd", ctypes.byref(a), ws, wsb, _stream())
         return n_prime, fiber_time, tmean, tvar, tt
 
     def loss_finalize(self, d, n_prime, fiber_time, tvar, ci, pclass, pfiber, total_time, nfields,
@@ -1569,17 +1557,17 @@ class HipBackend:
         ci = ci.contiguous()
         sl = self._loss_layout(d)
         assert tvar.is_contiguous() and tvar.numel() == (d.NT if sl is None else 2 * d.NT)
-        self._lcall("loss_finalize", sl, d.G, d.NF, d.NC, n_prime.data_ptr(),
-                    fiber_time.data_ptr(), tvar.data_ptr(), ci.data_ptr(), float(pclass),
-                    float(pfiber), float(total_time), float(nfields), float(wutils), float(wvar),
-                    loss.data_ptr(), utils.data_ptr(), variance.data_ptr(), Gn.data_ptr(),
-                    Gf.data_ptr(), Gv.data_ptr(), _stream())
+        _call("pfsgnn_loss_finalize", None if sl is None else sl.ref, d.G, d.NF, d.NC,
+              n_prime.data_ptr(), fiber_time.data_ptr(), tvar.data_ptr(), ci.data_ptr(),
+              float(pclass), float(pfiber), float(total_time), float(nfields), float(wutils),
+              float(wvar), loss.data_ptr(), utils.data_ptr(), variance.data_ptr(), Gn.data_ptr(),
+              Gf.data_ptr(), Gv.data_ptr(), _stream())
         return loss, utils, variance, Gn, Gf, Gv
 
     def loss_bwd(self, d, y, sc, sh, Wd1, bd1, Wd2, bd2, ci, scale, sharpness, noiselevel, seed,
                  Gn, Gf, Gv, tmean, gscale, dWd1, dbd1, dWd2, dbd2, bn=None):
         """-> gxe; with ``bn`` = (mu1, inv1) of the final edge BatchNorm ->
-        (gxe, its backward sums' per-block partials) (pfsgnn_loss_bwd_bn).
+        (gxe, its backward sums' per-block partials) (pfsgnn_loss_bwd's bn_* fields).
         On a sliced general batch gxe is [F, EP] in slot order (0 at padding)
         and ``bn`` is not available (Engine.loss_bnstat gives None)."""
         sl = self._loss_layout(d)
@@ -1606,7 +1594,7 @@ class HipBackend:
             part = self.empty(lib().pfsgnn_loss_bn_parts(d.G, d.NF, d.NC), 2 * d.F)
             a.bn_mu1, a.bn_inv1, a.bn_part = mu1.data_ptr(), inv1.data_ptr(), part.data_ptr()
         ws, wsb = self._wsargs(d)
-        _call("pfsgnn_loss_bwd_ex", ctypes.byref(a), ws, wsb, _stream())
+        _call("pfsgnn_loss_bwd", ctypes.byref(a), ws, wsb, _stream())
         return gxe if bn is None else (gxe, part)
 
     # ------------------------------------------------------------ graph building

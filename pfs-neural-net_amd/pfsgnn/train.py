@@ -173,7 +173,7 @@ def _loss_apply(graph, class_info, pclass, pfiber, sharpness, want_time, gnn, se
         if lay.sp.sl is None:
             raise NotImplementedError(
                 "loss_function on a general (non-complete) batch runs on the fused sliced "
-                "kernels (pfsgnn_sl_loss_*) only, and this batch is on the composed path: "
+                "kernels (pfsgnn_loss_fwd / _bwd with sl) only, and this batch is on the composed path: "
                 "unset PFSGNN_SLICED=0, keep the classes per graph within "
                 "pfsgnn_sliced_max_nc (at most 128) and use an fp32 edge-state path "
                 "(not \"bf16\" / \"bf16y\"); or materialise out.x_e and write the loss in torch")

@@ -454,7 +454,7 @@ class EmuBackend:
         out = self._target_bwd(d, y, sc, sh, Rs, Wt1, g_hsum, dWt1, want_gxe=want_gxe)
         if g_xs is not None:
             self.lin_t(Wt1, 0, d.F, out[0], out=g_xs, add=True)
-        if bn_sums is not None:   # pfsgnn_target_bwd_bn: per-64-fiber partials [nb][32]
+        if bn_sums is not None:   # pfsgnn_target_bwd's bn_part: per-64-fiber partials [nb][32]
             Yp, mu, var, eps = bn_sums
             O, NS = g_xs.shape
             xh = (Yp - mu[:, None]) / torch.sqrt(var[:, None] + eps)

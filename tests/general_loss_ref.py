@@ -2,7 +2,7 @@
 
 The reference objective (train.py:29-80) indexes edges by position, which only
 means something on the complete fiber-major graph.  The general form indexes
-by ``edge_index`` (include/pfsgnn.h, pfsgnn_sl_loss_fwd); it is restated here
+by ``edge_index`` (include/pfsgnn.h, pfsgnn_loss_args' sl); it is restated here
 from ``oracle.ref_scatter.scatter`` and ``oracle.ref_train.softfloor``:
 
 * ``time_e = softplus(decoder_e(x_e)) * total_time / NC`` (train.py:42);

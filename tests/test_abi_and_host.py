@@ -89,7 +89,7 @@ def test_removed_edge_entry_points_are_gone(lib):
     bound, nor named in the header."""
     from pfsgnn import native
     header = open(os.path.join(ROOT, "include", "pfsgnn.h")).read()
-    assert lib.pfsgnn_version().decode() == native.ABI_VERSION == "pfsgnn 0.2 gfx950"
+    assert lib.pfsgnn_version().decode() == native.ABI_VERSION == "pfsgnn 0.3 gfx950"
     for name in REMOVED_EDGE_ENTRY_POINTS:
         assert not hasattr(lib, name), f"libpfsgnn.so still exports {name}"
         assert name not in native._SIGS
@@ -98,16 +98,40 @@ def test_removed_edge_entry_points_are_gone(lib):
         assert hasattr(lib, "pfsgnn_" + op) and len(native._SIGS["pfsgnn_" + op][0]) == 4
 
 
-def test_library_of_another_abi_version_is_refused(tmp_path):
-    """A library left over from another tree (PFSGNN_LIB_PATH, a variant build)
-    can export the edge ops' names with the old signatures; the binding refuses
-    it by its version string instead of calling into it."""
+# the loss ops' entry points before each op had one (pfsgnn_loss_args)
+REMOVED_LOSS_ENTRY_POINTS = [
+    "pfsgnn_loss_bwd_bn", "pfsgnn_sl_loss_fwd", "pfsgnn_sl_loss_finalize", "pfsgnn_sl_loss_bwd",
+    "pfsgnn_loss_fwd_ex", "pfsgnn_loss_bwd_ex"]
+
+
+def test_removed_loss_entry_points_are_gone(lib):
+    """The loss forward and backward have one entry point each, with the struct
+    signature; finalize has one, led by the sliced layout; the six other names
+    are neither exported, bound (native.exported_symbols, _SIGS), nor named in
+    the header."""
+    import ctypes
+    from pfsgnn import native
+    header = open(os.path.join(ROOT, "include", "pfsgnn.h")).read()
+    for name in REMOVED_LOSS_ENTRY_POINTS:
+        assert not hasattr(lib, name), f"libpfsgnn.so still exports {name}"
+        assert name not in native._SIGS and name not in native.exported_symbols()
+        assert not re.search(r"\b%s\b" % name, header), f"pfsgnn.h still names {name}"
+    assert not [n for n in native._SIGS if n.startswith("pfsgnn_sl_loss")]
+    for op in ("pfsgnn_loss_fwd", "pfsgnn_loss_bwd"):
+        assert hasattr(lib, op)
+        assert native._SIGS[op][0] == [ctypes.POINTER(native.LossArgs), native.P, native.SZ, native.P]
+    assert native._SIGS["pfsgnn_loss_finalize"][0][0] is native.SLP
+    assert len(native._SIGS["pfsgnn_loss_finalize"][0]) == 21
+
+
+def _stand_in_library_is_refused(tmp_path, source):
+    """native.lib() on a stand-in library built from ``source`` -> its refusal text."""
     import shutil
     import sys
     cc = shutil.which("cc") or shutil.which("gcc") or "/opt/rocm/llvm/bin/clang"
-    src = tmp_path / "old.c"
-    src.write_text('const char* pfsgnn_version(void) { return "pfsgnn 0.1 gfx950"; }\n')
-    so = tmp_path / "libpfsgnn_old.so"
+    src = tmp_path / "standin.c"
+    src.write_text(source)
+    so = tmp_path / "libpfsgnn_standin.so"
     subprocess.run([cc, "-shared", "-fPIC", "-o", str(so), str(src)], check=True)
     code = ("import sys; sys.path.insert(0, %r)\n"
             "from pfsgnn import native\n"
@@ -116,7 +140,45 @@ def test_library_of_another_abi_version_is_refused(tmp_path):
     r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, PFSGNN_LIB_PATH=str(so)),
                        capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stderr[-2000:]
-    assert "REFUSED" in r.stdout and "pfsgnn 0.1 gfx950" in r.stdout and "rebuild" in r.stdout
+    assert "REFUSED" in r.stdout, r.stdout
+    return r.stdout
+
+
+def test_library_of_another_abi_version_is_refused(tmp_path):
+    """A library left over from another tree (PFSGNN_LIB_PATH, a variant build)
+    can export the edge ops' names with the old signatures; the binding refuses
+    it by its version string instead of calling into it.  "pfsgnn 0.2" is the
+    library whose pfsgnn_loss_fwd / pfsgnn_loss_bwd took positional arguments:
+    the same names as today's with other signatures."""
+    for old in ("pfsgnn 0.1 gfx950", "pfsgnn 0.2 gfx950"):
+        out = _stand_in_library_is_refused(
+            tmp_path, 'const char* pfsgnn_version(void) { return "%s"; }\n' % old)
+        assert old in out and "pfsgnn 0.3 gfx950" in out and "rebuild" in out
+
+
+def test_library_with_another_edge_struct_layout_is_refused(tmp_path):
+    """A library of the right version whose pfsgnn_edge_args_bytes disagrees with
+    one of this binding's six edge argument structs is refused when it loads,
+    as for LossArgs and TrainRecordArgs."""
+    import ctypes
+    from pfsgnn import native
+    sizes = [ctypes.sizeof(c) for c in native.EDGE_ARGS.values()]
+    sizes[3] += 8                                             # target_bwd: one field more
+    special = {
+        "pfsgnn_version": 'const char* pfsgnn_version(void) { return "%s"; }' % native.ABI_VERSION,
+        "pfsgnn_loss_args_bytes": "unsigned long pfsgnn_loss_args_bytes(void) { return %d; }"
+                                  % ctypes.sizeof(native.LossArgs),
+        "pfsgnn_train_record_args_bytes":
+            "unsigned long pfsgnn_train_record_args_bytes(void) { return %d; }"
+            % ctypes.sizeof(native.TrainRecordArgs),
+        "pfsgnn_edge_args_bytes":
+            "unsigned long pfsgnn_edge_args_bytes(int op) { static const unsigned long s[6] = {%s}; "
+            "return op >= 0 && op < 6 ? s[op] : 0; }" % ", ".join(map(str, sizes)),
+    }
+    source = "\n".join(special.get(n, "int %s(void) { return 0; }" % n) for n in native._SIGS)
+    out = _stand_in_library_is_refused(tmp_path, source + "\n")
+    assert "pfsgnn_edge_args_bytes(3) = %d" % sizes[3] in out
+    assert "TargetBwdArgs has %d bytes" % (sizes[3] - 8) in out and "rebuild" in out
 
 
 def test_edge_ops_refuse_bad_arguments_before_any_launch(lib):

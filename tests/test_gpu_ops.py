@@ -273,7 +273,7 @@ def test_loss_ops(hb, G, NF, NC):
         close(gxh, gxe, rtol=2e-3, atol=1e-4, name="loss gxe")
         for a, b, nm in zip(gh, ge, ["dWd1", "dbd1", "dWd2", "dbd2"]):
             close(a, b, rtol=2e-3, atol=1e-4, name=nm)
-        # the BatchNorm-sums arm (pfsgnn_loss_bwd_bn): the same gradient, bitwise,
+        # the BatchNorm-sums arm (pfsgnn_loss_bwd's bn_* fields): the same gradient, bitwise,
         # plus per-block partials of sum g and sum g (y - mu1) inv1
         mu1, var1 = r(F, gen=gen), r(F, gen=gen).abs() + 0.5
         inv1 = 1.0 / torch.sqrt(var1 + 1e-5)

@@ -191,7 +191,7 @@ def lib():
 
 def test_abi_struct_sizes_and_version(lib):
     from pfsgnn import native
-    assert lib.pfsgnn_version().decode() == native.ABI_VERSION == "pfsgnn 0.2 gfx950"
+    assert lib.pfsgnn_version().decode() == native.ABI_VERSION == "pfsgnn 0.3 gfx950"
     assert lib.pfsgnn_loss_args_bytes() == ctypes.sizeof(native.LossArgs)
     assert native.LossArgs.bn_part.offset == ctypes.sizeof(native.LossArgs) - 8
     assert native.LossArgs.sl.offset == 16
@@ -224,16 +224,28 @@ def test_new_entry_points_refuse_bad_arguments_before_any_launch(lib):
             assert w in err, (err, w)
 
     sliced = native.Sliced(fib=FAKE, base=FAKE, len=FAKE, cls=FAKE, pco=FAKE, EP=32, E=20, maxdeg=2)
-    for fn in ("pfsgnn_loss_fwd_ex", "pfsgnn_loss_bwd_ex"):
+    slp = ctypes.pointer(sliced)
+    max_nc = ctypes.c_int(0)
+    assert lib.pfsgnn_sliced_max_nc(10, ctypes.byref(max_nc)) == 0 and max_nc.value > 0
+    for fn in ("pfsgnn_loss_fwd", "pfsgnn_loss_bwd"):
         refused(fn, (None, None, 0, None), "null")
         refused(fn, (ctypes.byref(loss_args(pos_user=FAKE)), None, 0, None), "sl", "pos_user")
-        refused(fn, (ctypes.byref(loss_args(sl=ctypes.pointer(sliced))), None, 0, None), "pos_user")
+        refused(fn, (ctypes.byref(loss_args(sl=slp)), None, 0, None), "pos_user")
         refused(fn, (ctypes.byref(loss_args(bn_part=FAKE)), None, 0, None), "bn_mu1", "bn_part")
-        refused(fn, (ctypes.byref(loss_args(sl=ctypes.pointer(sliced), pos_user=FAKE, bn_mu1=FAKE,
+        refused(fn, (ctypes.byref(loss_args(sl=slp, pos_user=FAKE, bn_mu1=FAKE,
                                             bn_inv1=FAKE, bn_part=FAKE)), None, 0, None), "sl", "bn_part")
-        refused(fn, (ctypes.byref(loss_args(F=11)), None, 0, None), "Fdim")
-        refused(fn, (ctypes.byref(loss_args(y=None)), None, 0, None), "null")
-        refused(fn, (ctypes.byref(loss_args()), None, 0, None), "workspace")
+        # the dense and the sliced form of the op, each under the op's one name
+        for form in (dict(), dict(sl=slp, pos_user=FAKE)):
+            refused(fn, (ctypes.byref(loss_args(F=11, **form)), None, 0, None), "Fdim")
+            refused(fn, (ctypes.byref(loss_args(y=None, **form)), None, 0, None), "null")
+            refused(fn, (ctypes.byref(loss_args(**form)), None, 0, None), "workspace")
+        refused(fn, (ctypes.byref(loss_args(sl=slp, pos_user=FAKE, NC=max_nc.value + 1)), None, 0,
+                     None), "pfsgnn_sliced_max_nc")
+    fin = [1, 16, 2] + [FAKE] * 4 + [0.1, 0.1, 42.0, 10.0, 2000.0, 1.0] + [FAKE] * 6 + [None]
+    for sl in (None, slp):
+        refused("pfsgnn_loss_finalize", [sl, 1, 1, 2] + fin[3:], "bad dims")
+        refused("pfsgnn_loss_finalize", [sl] + fin[:3] + [None] + fin[4:], "null")
+        refused("pfsgnn_loss_finalize", [sl] + fin[:-2] + [None, None], "null")
     refused("pfsgnn_softfloor_record", (None, FAKE, None), "null")
     refused("pfsgnn_softfloor_record", (FAKE, FAKE + 4, None), "aligned")
     refused("pfsgnn_train_advance", (FAKE, FAKE, 0.0, 20.0, 0, FAKE, FAKE, None), "nepochs")
