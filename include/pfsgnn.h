@@ -918,6 +918,57 @@ int pfsgnn_loss_bn_parts(int G, int NF, int NC);
 /* sf [4] from the device float *sharpness (one thread; train.py:26) */
 int pfsgnn_softfloor_record(const float* sharpness, float* sf, void* stream);
 
+/* ---------------------------------------------------------------- hard schedule
+ * The integer evaluation of an allocation: what train.py:50 keeps as a comment
+ * (n = scatter(torch.floor(visited), tgt, ...)), what the "optionally produce
+ * hard counts & diagnostics" branch of train.py:74 announces, and the rounding
+ * to whole visits of train.py:257 (np.round(raw / class_req) * class_req).
+ * One pass over the lazy edge state (y, sc, sh) the loss ops stream; no noise,
+ * no sharpness, no seed.  Every edge e = (src_e, tgt_e) is indexed by
+ * edge_index, as in the loss ops' general form:
+ *   x = fmaf(y, sc, sh) per channel (y when sc is NULL);
+ *   time_e = softplus(decoder_e(x)) * scale   (the loss kernels' FMA order,
+ *            threshold 20; scale = TOTAL_TIME / NC);
+ *   v_e = time_e / T[tgt_e]   as one IEEE fp32 division (T = ci row 0);
+ *   visits_e = (int32) floorf(v_e)  for rounding = 0,
+ *              (int32) rintf(v_e)   for rounding = 1 (half to even, np.round);
+ *   n_hard_c = sum of visits_e over tgt_e = c, int32 (exact);
+ *   fiber_time_f = sum of (float)visits_e * T[tgt_e] over src_e = f: fp32
+ *            products summed in fp32 in a fixed order (0 without edges);
+ *   completeness_c = n_hard_c / (N_c / nfields)   (two IEEE divisions, the form
+ *            of pfsgnn_train_record; N = ci row 1);
+ *   utility_g = min over the graph's classes (a class without edges: 0; a NaN
+ *            propagates);  over_g = the graph's fibers with fiber_time_f >
+ *            total_time (int32);  worst_g = max_f fiber_time_f.
+ * Batch: sl + pos_user (both, or neither) a sliced general batch, y [F][sl->EP];
+ * else a complete batch, y canonical [F][G*NF*NC], whose caller order is given
+ * by mode and perm exactly as pfsgnn_edges_from_canonical takes them -- there is
+ * no positional noise counter, so every complete order is accepted (0: a
+ * permutation, 1: fiber-major, 2: canonical).  visits [E] is written in the
+ * CALLER's edge order; n_hard, completeness [G*NC]; fiber_time [G*NF]; utility,
+ * over, worst [G].  Workspace: pfsgnn_workspace_bytes.  Nothing allocates,
+ * synchronises or uses float atomics: capturable and bitwise reproducible.
+ * Refused before any launch: a null struct, sl without pos_user or the
+ * reverse, sl with perm, mode 0 without perm, rounding outside {0, 1}, Fdim
+ * outside 8 / 10 / 16, NC above pfsgnn_sliced_max_nc with sl, a null output or
+ * input, a workspace too small. */
+typedef struct pfsgnn_schedule_args {
+  int G, NF, NC, F;
+  const pfsgnn_sliced_t* sl;
+  const int* pos_user;
+  int mode;
+  const int32_t* perm;
+  const float *y, *sc, *sh, *Wd1, *bd1, *Wd2, *bd2, *ci;
+  float scale, total_time, nfields;
+  int rounding;
+  int32_t *visits, *n_hard;
+  float *fiber_time, *completeness, *utility;
+  int32_t* over;
+  float* worst;
+} pfsgnn_schedule_args;
+size_t pfsgnn_schedule_args_bytes(void);
+int pfsgnn_schedule(const pfsgnn_schedule_args* a, void* ws, size_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------- training loop
  * The per-epoch bookkeeping of train.py:133-165 as three small launches, so a
  * whole epoch (these, the forward, the loss, the backward, pfsgnn_adam) is one
@@ -953,6 +1004,27 @@ typedef struct pfsgnn_train_record_args {
 } pfsgnn_train_record_args;
 size_t pfsgnn_train_record_args_bytes(void);
 int pfsgnn_train_record(const pfsgnn_train_record_args* a, void* stream);
+/* pfsgnn_train_record_hard -- after pfsgnn_schedule (rounding 0) in a loop that
+ * tracks the integer objective.  One thread sums utility [G] and over [G] in
+ * the order g = 0 .. G-1 into hard_objective / hard_overtime [nepochs] at
+ * *epoch (an *epoch outside [0, nepochs) writes no history), then, in fp32,
+ * improved_hard = hard utility > *best_hard_utility (a NaN: false; the start
+ * value is 0, train.py:117; no sharpness condition -- the count does not depend
+ * on it); *improved_hard = 0 / 1, and when 1 also *best_hard_utility and
+ * *best_hard_epoch. */
+typedef struct pfsgnn_train_record_hard_args {
+  int G;
+  long long nepochs;
+  const long long* epoch;
+  const float* utility;
+  const int32_t* over;
+  float* hard_objective;
+  int32_t *hard_overtime, *improved_hard;
+  float* best_hard_utility;
+  long long* best_hard_epoch;
+} pfsgnn_train_record_hard_args;
+size_t pfsgnn_train_record_hard_args_bytes(void);
+int pfsgnn_train_record_hard(const pfsgnn_train_record_hard_args* a, void* stream);
 /* pfsgnn_copy_if -- after pfsgnn_adam (train.py:150-158: the best time, fiber
  * time and completion row come from the forward before the update, the
  * checkpointed weights and optimiser state are those after optimizer.step()).

@@ -7,45 +7,6 @@
 #include <algorithm>
 #include <cmath>
 
-#define EDGE_PROLOGUE                                                       \
-  const int t = threadIdx.x, lane = t & 63;                                 \
-  const int wave = __builtin_amdgcn_readfirstlane(t >> 6);                  \
-  const int bx = PF_LOGICAL_BLOCK(geo);                                     \
-  if (bx >= geo.nblocks) return;                                            \
-  const int ks = bx % geo.KS, grp = bx / geo.KS;                            \
-  const int fg = grp % geo.NFG, gg = grp / geo.NFG;                         \
-  const int f = fg * 64 + lane;                                             \
-  const bool fvalid = f < geo.NF;                                           \
-  const long long n = (long long)gg * geo.NF + (fvalid ? f : 0);            \
-  const long long nbase = (long long)gg * geo.NF + (long long)fg * 64;      \
-  const int nvalid = min(64, geo.NF - fg * 64);                             \
-  const int c0 = ks * geo.CPS, c1 = min(geo.NC, c0 + geo.CPS);              \
-  const long long E = geo.E, NS = geo.NS, NT = geo.NT;                      \
-  (void)E; (void)NS; (void)NT; (void)n; (void)nbase; (void)nvalid; (void)t;
-
-#define CLASS_LOOP_BEGIN                                                    \
-  for (int c = c0 + wave; c < c1; c += 4) {                                 \
-    const long long cn = (long long)gg * geo.NC + c;                        \
-    const long long e = cn * geo.NF + (fvalid ? f : 0);                     \
-    const long long eu = n * geo.NC + c; /* train.py's fiber-major position */
-
-#define CLASS_LOOP_END }
-
-// the next class's edge rows of this wave prefetched one iteration ahead
-// (register ring; the loop body is one long dependent chain per class)
-#define Y_PREFETCH_DECL(F)                                                    \
-  float yq[F];                                                              \
-  auto yload = [&](int cc) {                                                \
-    const long long ee = ((long long)gg * geo.NC + cc) * geo.NF + (fvalid ? f : 0); \
-    _Pragma("unroll") for (int k = 0; k < F; ++k)                           \
-      yq[k] = (fvalid && cc < c1) ? y[(long long)k * E + ee] : 0.f;         \
-  };                                                                        \
-  yload(c0 + wave);
-#define Y_TAKE(F, x)                                                          \
-  _Pragma("unroll") for (int k = 0; k < F; ++k)                             \
-    x[k] = sc ? fmaf(yq[k], sc[k], sh[k]) : yq[k];                          \
-  yload(c + 4);
-
 template <int F>
 __global__ __launch_bounds__(256) void k_loss_fwd(EdgeGeo geo, const float* __restrict__ y,
                                                   const float* __restrict__ sc,
@@ -228,18 +189,7 @@ __global__ __launch_bounds__(256) void k_loss_bwd(EdgeGeo geo, const float* __re
 }
 
 // ------------------------------------------------------------ layout
-// Canonical index k = (g*NC + c)*NF + f.  mode 0: user edge id = perm[k];
-// mode 1: user order is train.py's fiber-major (g*NF + f)*NC + c (graph.py /
-// cartesian_prod, train.py:94); mode 2: user order is already canonical.
-__device__ __forceinline__ long long user_index(long long k, int NF, int NC, int mode,
-                                                const int32_t* __restrict__ perm) {
-  if (mode == 2) return k;
-  if (mode == 0) return perm[k];
-  const long long gc = k / NF, f = k - gc * NF;
-  const long long g = gc / NC, c = gc - g * NC;
-  return (g * NF + f) * NC + c;
-}
-
+// (canonical index <-> the caller's edge: user_index, pfsgnn_loss_core.h)
 __global__ void k_layout_init(int32_t* status) {
   if (threadIdx.x == 0) { status[0] = 1; status[1] = 1; status[2] = 1; }
 }
@@ -354,15 +304,6 @@ int check_dims(const char* where, int G, int NF, int NC, int F) {
   if (NC > 256) return pf::fail(where, "NC > 256 is not supported by the dense edge kernels");
   if (F != 8 && F != 10 && F != 16) return pf::fail(where, "unsupported Fdim (8, 10, 16)");
   return 0;
-}
-// the loss kernels' grid: class splits to about PFSGNN_LOSS_BLOCKS blocks
-// (A/B knob; default PF_TARGET_BLOCKS)
-EdgeGeo loss_geo(int G, int NF, int NC) {
-  static const int tb = [] {
-    const char* e = getenv("PFSGNN_LOSS_BLOCKS");
-    return e && atoi(e) > 0 ? atoi(e) : PF_TARGET_BLOCKS;
-  }();
-  return make_geo(G, NF, NC, tb);
 }
 }  // namespace
 

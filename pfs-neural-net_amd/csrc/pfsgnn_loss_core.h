@@ -8,6 +8,7 @@
 #include "../../include/pfsgnn.h"
 
 #include <cmath>
+#include <cstdlib>
 
 __device__ __forceinline__ void wave_lds_sync() {
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -105,6 +106,28 @@ struct EdgeLoss {
   }
 };
 
+// EdgeLoss<F>::run up to `time` alone -- decoder_e and softplus * scale in the
+// same FMA order, without softfloor's trigonometry: what the hard schedule
+// (pfsgnn_schedule.hip) floors or rounds
+template <int F>
+struct EdgeTime {
+  float pred, time;
+  __device__ __forceinline__ void run(const float (&x)[F], const float* __restrict__ Wd1,
+                                      const float* __restrict__ bd1, const float* __restrict__ Wd2,
+                                      const float* __restrict__ bd2, float scale) {
+    pred = bd2[0];
+#pragma unroll
+    for (int j = 0; j < F; ++j) {
+      float s = bd1[j];
+#pragma unroll
+      for (int k = 0; k < F; ++k) s = fmaf(Wd1[j * F + k], x[k], s);
+      pred = fmaf(Wd2[j], lrelu(s), pred);
+    }
+    const float sp = pred > 20.f ? pred : log1pf(expf(pred));  // F.softplus (threshold 20)
+    time = sp * scale;
+  }
+};
+
 // decoder_e's weights staged in LDS (read as broadcasts inside the edge loop):
 // held in SGPRs they overflowed the scalar file (119 / 139 SGPR spills, each
 // use a v_readlane in the loop)
@@ -127,6 +150,121 @@ __device__ __forceinline__ const float* dec_base(const DecW<F>& d) {
   asm volatile("" : "+v"(lo));
   return d.w + lo;
 }
+
+// ---- the dense loss kernels' iteration (pfsgnn_loss.hip, pfsgnn_schedule.hip):
+// EdgeGeo's block -> (graph, 64-fiber group, class split), lane = fiber, wave w
+// the classes c0 + w, c0 + w + 4, ...
+#define EDGE_PROLOGUE                                                       \
+  const int t = threadIdx.x, lane = t & 63;                                 \
+  const int wave = __builtin_amdgcn_readfirstlane(t >> 6);                  \
+  const int bx = PF_LOGICAL_BLOCK(geo);                                     \
+  if (bx >= geo.nblocks) return;                                            \
+  const int ks = bx % geo.KS, grp = bx / geo.KS;                            \
+  const int fg = grp % geo.NFG, gg = grp / geo.NFG;                         \
+  const int f = fg * 64 + lane;                                             \
+  const bool fvalid = f < geo.NF;                                           \
+  const long long n = (long long)gg * geo.NF + (fvalid ? f : 0);            \
+  const long long nbase = (long long)gg * geo.NF + (long long)fg * 64;      \
+  const int nvalid = min(64, geo.NF - fg * 64);                             \
+  const int c0 = ks * geo.CPS, c1 = min(geo.NC, c0 + geo.CPS);              \
+  const long long E = geo.E, NS = geo.NS, NT = geo.NT;                      \
+  (void)E; (void)NS; (void)NT; (void)n; (void)nbase; (void)nvalid; (void)t;
+
+#define CLASS_LOOP_BEGIN                                                    \
+  for (int c = c0 + wave; c < c1; c += 4) {                                 \
+    const long long cn = (long long)gg * geo.NC + c;                        \
+    const long long e = cn * geo.NF + (fvalid ? f : 0);                     \
+    const long long eu = n * geo.NC + c; /* train.py's fiber-major position */
+
+#define CLASS_LOOP_END }
+
+// the next class's edge rows of this wave prefetched one iteration ahead
+// (register ring; the loop body is one long dependent chain per class)
+#define Y_PREFETCH_DECL(F)                                                    \
+  float yq[F];                                                              \
+  auto yload = [&](int cc) {                                                \
+    const long long ee = ((long long)gg * geo.NC + cc) * geo.NF + (fvalid ? f : 0); \
+    _Pragma("unroll") for (int k = 0; k < F; ++k)                           \
+      yq[k] = (fvalid && cc < c1) ? y[(long long)k * E + ee] : 0.f;         \
+  };                                                                        \
+  yload(c0 + wave);
+#define Y_TAKE(F, x)                                                          \
+  _Pragma("unroll") for (int k = 0; k < F; ++k)                             \
+    x[k] = sc ? fmaf(yq[k], sc[k], sh[k]) : yq[k];                          \
+  yload(c + 4);
+
+// Canonical index k = (g*NC + c)*NF + f.  mode 0: user edge id = perm[k];
+// mode 1: user order is train.py's fiber-major (g*NF + f)*NC + c (graph.py /
+// cartesian_prod, train.py:94); mode 2: user order is already canonical.
+__device__ __forceinline__ long long user_index(long long k, int NF, int NC, int mode,
+                                                const int32_t* __restrict__ perm) {
+  if (mode == 2) return k;
+  if (mode == 0) return perm[k];
+  const long long gc = k / NF, f = k - gc * NF;
+  const long long g = gc / NC, c = gc - g * NC;
+  return (g * NF + f) * NC + c;
+}
+
+
+// the loss kernels' grid: class splits to about PFSGNN_LOSS_BLOCKS blocks
+// (A/B knob; default PF_TARGET_BLOCKS)
+inline EdgeGeo loss_geo(int G, int NF, int NC) {
+  static const int tb = [] {
+    const char* e = getenv("PFSGNN_LOSS_BLOCKS");
+    return e && atoi(e) > 0 ? atoi(e) : PF_TARGET_BLOCKS;
+  }();
+  return make_geo(G, NF, NC, tb);
+}
+
+// ---- the sliced loss kernels' iteration (pfsgnn_sl_loss.hip, pfsgnn_schedule.hip;
+// `sl` a pfm::SlGeo, `geo` pfm::sl_geo's): a lane owns an edge, four steps per
+// iteration
+#define SLL_PROLOGUE                                                                   \
+  const int t = threadIdx.x, lane = t & 63;                                            \
+  const int wave = __builtin_amdgcn_readfirstlane(t >> 6);                             \
+  const int q4 = lane >> 4, j16 = lane & 15;                                           \
+  const int bx = blockIdx.x;                                                           \
+  const int ks = bx % geo.KS, grp = bx / geo.KS;                                       \
+  const int gg = grp / geo.NFG;                                                        \
+  const int slc = 4 * grp + wave;                                                      \
+  const int fib = sl.fib[slc * 16 + j16];   /* global fiber of the lane, -1: none */   \
+  const int pb = __builtin_amdgcn_readfirstlane(sl.base[slc]);                         \
+  const int Ls = __builtin_amdgcn_readfirstlane(sl.len[slc]);                          \
+  /* split ks of KS: steps [k0, k1) of the slice, four per iteration */                \
+  const int k0 = (int)(((long long)Ls * ks) / geo.KS);                                 \
+  const int k1 = (int)(((long long)Ls * (ks + 1)) / geo.KS);                           \
+  const int nit = (k1 - k0 + 3) >> 2;                                                  \
+  const int NC = geo.NC;                                                               \
+  const long long EP = geo.E, NS = geo.NS;                                             \
+  const long long cn0 = (long long)gg * NC;                                            \
+  const long long p0 = (long long)pb + 16ll * k0 + lane;                               \
+  (void)NS; (void)t;
+
+// the lane's edge of one iteration: channel rows, class byte, caller edge id
+// (steps beyond the split load nothing: class 0xFF, edge -1, rows 0)
+template <int F>
+struct SlEdge {
+  float y[F];
+  int cls, pos;
+  bool in;   // the step belongs to this block's split (its position is ours to write)
+};
+#define SLL_LOAD_DECL(F)                                                               \
+  auto load = [&](int i) {                                                             \
+    SlEdge<F> r;                                                                       \
+    r.in = k0 + 4 * i + q4 < k1;                                                       \
+    const long long p = p0 + 64ll * i;                                                 \
+    r.cls = r.in ? (int)sl.cls[p] : 0xFF;                                              \
+    r.pos = r.in ? pos_user[p] : -1;                                                   \
+    _Pragma("unroll") for (int k = 0; k < F; ++k)                                      \
+      r.y[k] = r.in ? y[(long long)k * EP + p] : 0.f;                                  \
+    return r;                                                                          \
+  };
+// validity and the class clamped to 0 (padding 0xFF, steps beyond the split and
+// lanes without a fiber never index a class table with their raw byte)
+#define SLL_STEP(e)                                                                    \
+  const bool ev = (e).in && fib >= 0 && (e).cls < NC && (e).pos >= 0;                  \
+  const int cl = ev ? (e).cls : 0;                                                     \
+  const long long cn = cn0 + cl;
 
 __device__ __forceinline__ double wave_dsum(double v) {
 #pragma unroll

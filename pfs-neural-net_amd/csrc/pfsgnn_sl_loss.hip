@@ -36,53 +36,6 @@ constexpr int MAXC = pfm::SL_MAX_NC;
 // different classes spread over the LDS banks)
 constexpr int CST = 5;
 
-#define SLL_PROLOGUE                                                                   \
-  const int t = threadIdx.x, lane = t & 63;                                            \
-  const int wave = __builtin_amdgcn_readfirstlane(t >> 6);                             \
-  const int q4 = lane >> 4, j16 = lane & 15;                                           \
-  const int bx = blockIdx.x;                                                           \
-  const int ks = bx % geo.KS, grp = bx / geo.KS;                                       \
-  const int gg = grp / geo.NFG;                                                        \
-  const int slc = 4 * grp + wave;                                                      \
-  const int fib = sl.fib[slc * 16 + j16];   /* global fiber of the lane, -1: none */   \
-  const int pb = __builtin_amdgcn_readfirstlane(sl.base[slc]);                         \
-  const int Ls = __builtin_amdgcn_readfirstlane(sl.len[slc]);                          \
-  /* split ks of KS: steps [k0, k1) of the slice, four per iteration */                \
-  const int k0 = (int)(((long long)Ls * ks) / geo.KS);                                 \
-  const int k1 = (int)(((long long)Ls * (ks + 1)) / geo.KS);                           \
-  const int nit = (k1 - k0 + 3) >> 2;                                                  \
-  const int NC = geo.NC;                                                               \
-  const long long EP = geo.E, NS = geo.NS;                                             \
-  const long long cn0 = (long long)gg * NC;                                            \
-  const long long p0 = (long long)pb + 16ll * k0 + lane;                               \
-  (void)NS; (void)t;
-
-// the lane's edge of one iteration: channel rows, class byte, caller edge id
-// (steps beyond the split load nothing: class 0xFF, edge -1, rows 0)
-template <int F>
-struct SlEdge {
-  float y[F];
-  int cls, pos;
-  bool in;   // the step belongs to this block's split (its position is ours to write)
-};
-#define SLL_LOAD_DECL(F)                                                               \
-  auto load = [&](int i) {                                                             \
-    SlEdge<F> r;                                                                       \
-    r.in = k0 + 4 * i + q4 < k1;                                                       \
-    const long long p = p0 + 64ll * i;                                                 \
-    r.cls = r.in ? (int)sl.cls[p] : 0xFF;                                              \
-    r.pos = r.in ? pos_user[p] : -1;                                                   \
-    _Pragma("unroll") for (int k = 0; k < F; ++k)                                      \
-      r.y[k] = r.in ? y[(long long)k * EP + p] : 0.f;                                  \
-    return r;                                                                          \
-  };
-// validity and the class clamped to 0 (padding 0xFF, steps beyond the split and
-// lanes without a fiber never index a class table with their raw byte)
-#define SLL_STEP(e)                                                                    \
-  const bool ev = (e).in && fib >= 0 && (e).cls < NC && (e).pos >= 0;                  \
-  const int cl = ev ? (e).cls : 0;                                                     \
-  const long long cn = cn0 + cl;
-
 // sum over the lane's row of 16 lanes, in every lane of the row (fixed DPP tree)
 __device__ __forceinline__ float row_sum16(float v) {
   v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, false));

@@ -65,6 +65,29 @@ __global__ __launch_bounds__(256) void k_train_record(pfsgnn_train_record_args a
   }
 }
 
+// the integer objective's history rows and best-tracking (after
+// pfsgnn_schedule): one thread
+__global__ void k_train_record_hard(pfsgnn_train_record_hard_args a) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  const long long e = a.epoch[0];
+  float util = a.utility[0];
+  int over = a.over[0];
+  for (int g = 1; g < a.G; ++g) {
+    util += a.utility[g];
+    over += a.over[g];
+  }
+  if (e >= 0 && e < a.nepochs) {
+    a.hard_objective[e] = util;
+    a.hard_overtime[e] = over;
+  }
+  const bool improved = util > a.best_hard_utility[0];   // (a NaN utility compares false)
+  a.improved_hard[0] = improved ? 1 : 0;
+  if (improved) {
+    a.best_hard_utility[0] = util;
+    a.best_hard_epoch[0] = e;
+  }
+}
+
 // the jobs handed over with the launch (buffers whose address changes from
 // step to step in an eager loop; fixed by the capture in a replayed one)
 struct ExtraJobs {
@@ -132,6 +155,20 @@ extern "C" int pfsgnn_train_record(const pfsgnn_train_record_args* a, void* stre
              "pfsgnn_train_record", "null");
   hipLaunchKernelGGL(k_train_record, dim3(1), dim3(256), 0, as_stream(stream), *a);
   return pf::check_launch("pfsgnn_train_record");
+}
+
+extern "C" size_t pfsgnn_train_record_hard_args_bytes(void) {
+  return sizeof(pfsgnn_train_record_hard_args);
+}
+
+extern "C" int pfsgnn_train_record_hard(const pfsgnn_train_record_hard_args* a, void* stream) {
+  PF_REQUIRE(a, "pfsgnn_train_record_hard", "null argument struct");
+  PF_REQUIRE(a->G > 0 && a->nepochs > 0, "pfsgnn_train_record_hard", "bad dims");
+  PF_REQUIRE(a->epoch && a->utility && a->over && a->hard_objective && a->hard_overtime &&
+                 a->improved_hard && a->best_hard_utility && a->best_hard_epoch,
+             "pfsgnn_train_record_hard", "null");
+  hipLaunchKernelGGL(k_train_record_hard, dim3(1), dim3(64), 0, as_stream(stream), *a);
+  return pf::check_launch("pfsgnn_train_record_hard");
 }
 
 extern "C" int pfsgnn_copy_if(const int* flag, const pfsgnn_copy_job* jobs, int njobs,

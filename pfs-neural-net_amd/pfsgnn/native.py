@@ -211,6 +211,25 @@ class TrainRecordArgs(ctypes.Structure):
                         "best_utility", "best_loss", "best_epoch"))
 
 
+class TrainRecordHardArgs(ctypes.Structure):
+    """pfsgnn_train_record_hard_args: an epoch's integer-objective rows and
+    best-tracking."""
+    _fields_ = ([("G", I), ("nepochs", LL)]
+                + _ptrs("epoch", "utility", "over", "hard_objective", "hard_overtime",
+                        "improved_hard", "best_hard_utility", "best_hard_epoch"))
+
+
+class ScheduleArgs(ctypes.Structure):
+    """pfsgnn_schedule_args: the hard visit counts of a complete (mode, perm) or
+    sliced (sl + pos_user) batch."""
+    _fields_ = ([("G", I), ("NF", I), ("NC", I), ("F", I), ("sl", SLP)]
+                + _ptrs("pos_user") + [("mode", I)]
+                + _ptrs("perm", "y", "sc", "sh", "Wd1", "bd1", "Wd2", "bd2", "ci")
+                + [("scale", FL), ("total_time", FL), ("nfields", FL), ("rounding", I)]
+                + _ptrs("visits", "n_hard", "fiber_time", "completeness", "utility", "over",
+                        "worst"))
+
+
 class CopyJob(ctypes.Structure):
     """pfsgnn_copy_job: n 4-byte words from src to dst."""
     _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("n", LL)]
@@ -330,6 +349,10 @@ _SIGS = {
     "pfsgnn_train_record_args_bytes": ([], SZ),
     "pfsgnn_train_record": ([ctypes.POINTER(TrainRecordArgs), P], I),
     "pfsgnn_copy_if": ([P, P, I, ctypes.POINTER(CopyJob), I, LL, P], I),
+    "pfsgnn_schedule_args_bytes": ([], SZ),
+    "pfsgnn_schedule": ([ctypes.POINTER(ScheduleArgs), P, SZ, P], I),
+    "pfsgnn_train_record_hard_args_bytes": ([], SZ),
+    "pfsgnn_train_record_hard": ([ctypes.POINTER(TrainRecordHardArgs), P], I),
 }
 for _op, _cls in EDGE_ARGS.items():
     _SIGS["pfsgnn_" + _op] = ([ctypes.POINTER(_cls), P, SZ, P], I)
@@ -363,6 +386,8 @@ def lib():
         sizes = [("pfsgnn_loss_args_bytes", (), LossArgs),
                  ("pfsgnn_train_record_args_bytes", (), TrainRecordArgs)]
         sizes += [("pfsgnn_edge_args_bytes", (op,), cls) for op, cls in enumerate(EDGE_ARGS.values())]
+        sizes += [("pfsgnn_train_record_hard_args_bytes", (), TrainRecordHardArgs),
+                  ("pfsgnn_schedule_args_bytes", (), ScheduleArgs)]
         for query, qargs, cls in sizes:
             got, call = getattr(L, query)(*qargs), f"{query}({', '.join(map(str, qargs))})"
             if got != ctypes.sizeof(cls):
@@ -1487,6 +1512,23 @@ class HipBackend:
             setattr(a, k, _ptr(v))
         _call("pfsgnn_train_record", ctypes.byref(a), _stream())
 
+    def train_record_hard(self, d, nepochs, epoch, utility, over, hard_objective, hard_overtime,
+                          improved_hard, best_hard_utility, best_hard_epoch):
+        """An epoch's integer-objective rows and best-tracking from ``schedule``'s
+        utility / over [G] (pfsgnn_train_record_hard)."""
+        self._chk(utility, hard_objective, best_hard_utility)
+        assert over.dtype == hard_overtime.dtype == improved_hard.dtype == torch.int32
+        assert best_hard_epoch.dtype == epoch.dtype == torch.int64
+        assert min(hard_objective.numel(), hard_overtime.numel()) >= nepochs
+        assert min(utility.numel(), over.numel()) >= d.G
+        a = TrainRecordHardArgs(G=d.G, nepochs=int(nepochs))
+        for k, v in dict(epoch=epoch, utility=utility, over=over, hard_objective=hard_objective,
+                         hard_overtime=hard_overtime, improved_hard=improved_hard,
+                         best_hard_utility=best_hard_utility,
+                         best_hard_epoch=best_hard_epoch).items():
+            setattr(a, k, _ptr(v))
+        _call("pfsgnn_train_record_hard", ctypes.byref(a), _stream())
+
     @staticmethod
     def _copy_job_array(pairs):
         """(pfsgnn_copy_job array, largest word count) of (src, dst) tensor pairs
@@ -1549,6 +1591,48 @@ class HipBackend:
         ws, wsb = self._wsargs(d)
         _call("pfsgnn_loss_fwd", ctypes.byref(a), ws, wsb, _stream())
         return n_prime, fiber_time, tmean, tvar, tt
+
+    def schedule(self, d, y, sc, sh, Wd1, bd1, Wd2, bd2, ci, scale, total_time, nfields,
+                 rounding=0, mode=1, perm=None, out=None):
+        """The hard visit counts of the lazy edge state (pfsgnn_schedule) ->
+        (visits [E] int32 in the caller's edge order, n [NT] int32, fiber_time
+        [NS], completeness [NT], utility [G], over [G] int32, worst [G]).
+        A complete batch: y canonical [F, E], ``mode`` / ``perm`` its caller
+        order (0: perm, 1: fiber-major, 2: canonical); a sliced general batch
+        (``d.sp.sl``): y [F, EP] in slot order.  ``out``: the seven tensors to
+        write into (a loop's preallocated buffers)."""
+        sl = self._loss_layout(d)
+        if out is None:
+            i32 = dict(dtype=torch.int32, device=self.device)
+            out = (torch.empty(d.E, **i32), torch.empty(d.NT, **i32), self.empty(d.NS),
+                   self.empty(d.NT), self.empty(d.G), torch.empty(d.G, **i32), self.empty(d.G))
+        visits, n_hard, fiber_time, comp, utility, over, worst = out
+        assert visits.dtype == n_hard.dtype == over.dtype == torch.int32
+        self._chk(y, sc, sh, Wd1, bd1, Wd2, bd2, fiber_time, comp, utility, worst)
+        assert all(t.is_cuda and t.is_contiguous() for t in (visits, n_hard, over))
+        assert visits.numel() == d.E and n_hard.numel() == comp.numel() == d.NT
+        assert fiber_time.numel() == d.NS and min(utility.numel(), over.numel(), worst.numel()) == d.G
+        assert tuple(y.shape) == (d.F, d.EP), (tuple(y.shape), d.F, d.EP)
+        ci = ci.contiguous()
+        assert ci.numel() >= 2 * d.NT
+        a = ScheduleArgs(G=d.G, NF=d.NF, NC=d.NC, F=d.F, rounding=int(rounding))
+        if sl is not None:
+            a.sl, a.pos_user = sl.ref, sl.pos_user.data_ptr()
+        else:
+            a.mode = int(mode)
+            if perm is not None:
+                assert perm.dtype == torch.int32 and perm.is_cuda and perm.numel() == d.E
+                a.perm = perm.data_ptr()
+        a.y, a.sc, a.sh = y.data_ptr(), _ptr(sc), _ptr(sh)
+        a.Wd1, a.bd1, a.Wd2, a.bd2 = Wd1.data_ptr(), bd1.data_ptr(), Wd2.data_ptr(), bd2.data_ptr()
+        a.ci = ci.data_ptr()
+        a.scale, a.total_time, a.nfields = float(scale), float(total_time), float(nfields)
+        for k, v in zip(("visits", "n_hard", "fiber_time", "completeness", "utility", "over",
+                         "worst"), out):
+            setattr(a, k, v.data_ptr())
+        ws, wsb = self._wsargs(d)
+        _call("pfsgnn_schedule", ctypes.byref(a), ws, wsb, _stream())
+        return out
 
     def loss_finalize(self, d, n_prime, fiber_time, tvar, ci, pclass, pfiber, total_time, nfields,
                       wutils, wvar, gscale=1.0):

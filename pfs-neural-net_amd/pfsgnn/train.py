@@ -14,6 +14,7 @@ torch's global CPU generator -- so ``torch.manual_seed`` governs it as it
 governs the reference, a step is reproducible, and no RNG state lives on the
 device.
 """
+import collections
 import math
 import os
 import sys
@@ -199,6 +200,86 @@ def _loss_apply(graph, class_info, pclass, pfiber, sharpness, want_time, gnn, se
     return d, ci, outs
 
 
+# ---------------------------------------------------------------- hard schedule
+HardSchedule = collections.namedtuple(
+    "HardSchedule", "visits n fiber_time completeness utility over worst")
+
+_ROUNDINGS = {"floor": 0, "round": 1}
+
+
+def hard_schedule(graph, class_info, rounding="floor", *, gnn=None):
+    """The integer evaluation of an allocation: whole visits per edge and what
+    follows from them -- train.py:50's commented ``scatter(torch.floor(visited),
+    tgt)``, the "hard counts & diagnostics" of train.py:74, and, with
+    ``rounding="round"``, the rounding to whole visits of train.py:257
+    (``np.round``: half to even).  No noise, no sharpness, no seed.
+
+    ``graph`` is the output of ``GNN.forward`` (train or eval mode, grad on or
+    off); ``class_info`` as for ``loss_function``.  Every edge is indexed by
+    ``edge_index``: ``visits_e = floor(time_e / T[tgt_e])`` with ``time_e =
+    softplus(decoder_e(x_e)) * TOTAL_TIME / NC``, ``n_c`` sums visits over
+    ``tgt_e = c`` (int32), ``fiber_time_f`` sums ``visits_e * T[tgt_e]`` over
+    ``src_e = f``, ``completeness_c = n_c / (N_c / NFIELDS)``, ``utility`` [G]
+    its minimum per graph, ``over`` [G] the fibers above TOTAL_TIME and
+    ``worst`` [G] the largest fiber time.  So every complete edge order is
+    accepted (there is no positional noise counter), and sliced general
+    batches; ``visits`` [E] is in the caller's edge order.  The fused op
+    (pfsgnn_schedule) reads the lazy final edge state: ``out.x_e`` is not
+    materialised.  Returns a ``HardSchedule`` of device tensors without grad."""
+    return _hard_schedule(graph, class_info, rounding, gnn, None)
+
+
+def _hard_schedule(graph, class_info, rounding, gnn, out):
+    if rounding not in _ROUNDINGS:
+        raise ValueError(f"rounding must be 'floor' or 'round'; got {rounding!r}")
+    pf = graph.__dict__.get("_pf")
+    if pf is None or graph.__dict__.get("_pf_replaced"):
+        raise NotImplementedError("hard_schedule needs the BipartiteData returned by "
+                                  "pfsgnn.GNN.forward with its x_e untouched (the fused op reads "
+                                  "its edge state)")
+    model, d, lay, token, xe3, ectx = pf
+    if gnn is not None and gnn is not model:
+        raise NotImplementedError("hard_schedule: graph was produced by a different GNN than "
+                                  "`gnn` (the decoder of the GNN that made it is the one read)")
+    if lay.sp is not None and lay.sp.sl is None:
+        raise NotImplementedError(
+            "hard_schedule on a general (non-complete) batch runs on the fused sliced "
+            "kernel (pfsgnn_schedule with sl) only, and this batch is on the composed path: "
+            "unset PFSGNN_SLICED=0, keep the classes per graph within "
+            "pfsgnn_sliced_max_nc (at most 128) and use an fp32 edge-state path "
+            "(not \"bf16\" / \"bf16y\"); or materialise out.x_e and count in torch")
+    ci = _class_info_cm(class_info, d)
+    be = backend()
+    scale = float(config.TOTAL_TIME) / d.NC
+    if hasattr(be, "schedule"):
+        P = model._flat_params()
+        y, sc, sh = xe3
+        res = be.schedule(d, y, sc, sh, P["decoder_e.0.weight"], P["decoder_e.0.bias"],
+                          P["decoder_e.2.weight"], P["decoder_e.2.bias"], ci, scale,
+                          float(config.TOTAL_TIME), float(config.NFIELDS),
+                          rounding=_ROUNDINGS[rounding], mode=lay.mode, perm=lay.perm, out=out)
+        return HardSchedule(*res)
+    # a backend without the op (a CPU emulation of the op set): torch restatement
+    with torch.no_grad():
+        src, tgt = graph.edge_index[0], graph.edge_index[1]
+        time = model.edge_prediction(graph.x_e.detach(), scale=scale).reshape(-1)
+        T = ci[0][tgt]
+        v = time / T
+        visits = (torch.floor(v) if rounding == "floor" else torch.round(v)).to(torch.int32)
+        n = torch.zeros(d.NT, dtype=torch.int32, device=v.device).index_add_(0, tgt, visits)
+        ft = torch.zeros(d.NS, dtype=v.dtype, device=v.device).index_add_(
+            0, src, visits.to(v.dtype) * T)
+        comp = n.to(v.dtype) / (ci[1] / config.NFIELDS)
+        res = (visits, n, ft, comp, comp.view(d.G, d.NC).min(dim=1).values,
+               (ft.view(d.G, d.NF) > config.TOTAL_TIME).sum(dim=1).to(torch.int32),
+               ft.view(d.G, d.NF).max(dim=1).values)
+        if out is not None:
+            for o, r in zip(out, res):
+                o.copy_(r)
+            res = out
+    return HardSchedule(*res)
+
+
 # ---------------------------------------------------------------- training
 def complete_graph(class_info, nfibers, fdim, lo=2.0, hi=10.0):
     """train.py:88-104: fiber counter x_s, class_info x_t, fiber-major complete
@@ -234,13 +315,25 @@ class TrainLoop:
     counts epochs.  ``history()``, ``best()``, ``checkpoint()`` and
     ``best_checkpoint()`` read the device state (one sync each, at call time).
 
+    ``track_hard=True`` also evaluates the integer objective every epoch
+    (``hard_schedule`` with floor, pfsgnn_schedule into preallocated buffers)
+    right after ``train_record``: ``train_record_hard`` sums the graphs' hard
+    utilities and over-time fibers into the ``hard_objective`` /
+    ``hard_overtime`` history and tracks the best hard utility under strict
+    ``>`` from 0 (train.py:117; no ``min_sharp`` condition: the count does not
+    depend on the sharpness), and a second ``copy_if`` after Adam keeps that
+    epoch's visits, fiber_time and completion (``hard_best()``).  No parameter
+    snapshot is kept for it: the checkpoint criterion stays the soft one.  With
+    the default False the step issues exactly the launches listed above.
+
     One divergence from the reference: it rewrites the checkpoint file on every
     improvement; here the best state stays on the device until asked for.
     ``seed``: softfloor's noise seed before the first epoch (epoch e draws with
     seed + e - start_epoch + 1); None draws one from torch's CPU generator."""
 
     def __init__(self, gnn, optimizer, graph, class_info, nepochs, sharps, min_sharp, pclass,
-                 pfiber, seed=None, start_epoch=0, capture=True, record_completions=True):
+                 pfiber, seed=None, start_epoch=0, capture=True, record_completions=True,
+                 track_hard=False):
         from .optim import FusedAdam
         dist = torch.distributed
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
@@ -285,6 +378,17 @@ class TrainLoop:
         self._best_time, self._best_fiber_time, self._best_completion = buf(E), buf(NS), buf(NT)
         self._jobs = self._snap = None
         self._graph, self._warm = None, 0
+        # the integer objective (hard_schedule's outputs, its history and best state)
+        self.track_hard = bool(track_hard)
+        if self.track_hard:
+            i32 = torch.int32
+            self._hard = HardSchedule(buf(E, dtype=i32), buf(NT, dtype=i32), buf(NS), buf(NT),
+                                      buf(G), buf(G, dtype=i32), buf(G))
+            self._hard_objective, self._hard_overtime = buf(nepochs), buf(nepochs, dtype=i32)
+            self._improved_hard, self._best_hard_utility = buf(1, dtype=i32), buf(1)
+            self._best_hard_epoch = buf(1, dtype=torch.int64, fill=-1)
+            self._best_hard = (buf(E, dtype=i32), buf(NS), buf(NT))
+            self._hard_jobs = None
 
     # ------------------------------------------------------------ the three ops
     # (the backend's launches; torch restatements when it has none, for a CPU
@@ -336,6 +440,40 @@ class TrainLoop:
             for s, t in self._jobs + extra:
                 t.copy_(s.detach())
 
+    def _record_hard(self, out):
+        """The epoch's integer objective (floor) into the preallocated buffers,
+        its history rows and best-tracking."""
+        be = self._be
+        hs = _hard_schedule(out, self.class_info, "floor", None, self._hard)
+        if hasattr(be, "train_record_hard"):
+            d = out.__dict__["_pf"][1]
+            be.train_record_hard(d, self.nepochs, self._epoch, hs.utility, hs.over,
+                                 self._hard_objective, self._hard_overtime, self._improved_hard,
+                                 self._best_hard_utility, self._best_hard_epoch)
+            return
+        e = int(self._epoch)
+        util, over = hs.utility[0], hs.over[0]
+        for g in range(1, hs.utility.numel()):
+            util, over = util + hs.utility[g], over + hs.over[g]
+        if 0 <= e < self.nepochs:
+            self._hard_objective[e], self._hard_overtime[e] = util, over
+        improved = bool(util > self._best_hard_utility[0])
+        self._improved_hard.fill_(int(improved))
+        if improved:
+            self._best_hard_utility[0], self._best_hard_epoch[0] = util, e
+
+    def _copy_if_hard(self):
+        be = self._be
+        hs = self._hard
+        pairs = list(zip((hs.visits, hs.fiber_time, hs.completeness), self._best_hard))
+        if hasattr(be, "copy_if"):
+            if self._hard_jobs is None:
+                self._hard_jobs = be.copy_jobs(pairs)
+            be.copy_if(self._improved_hard, self._hard_jobs)
+        elif int(self._improved_hard):
+            for s, t in pairs:
+                t.copy_(s)
+
     def _build_snapshot(self):
         """The best state's buffers and the fixed part of the copy list (after
         the first step: Adam's flat moments and the counters' flat buffer exist)."""
@@ -368,9 +506,13 @@ class TrainLoop:
                                   self._seed, 0.3)
         loss, utils_g, n_prime, fiber_time, variance_g, time, loss_g = outs
         self._record(d, ci, loss_g, utils_g, variance_g, n_prime)
+        if self.track_hard:
+            self._record_hard(out)
         loss.backward()
         self.optimizer.step()
         self._copy_if(time, fiber_time)
+        if self.track_hard:
+            self._copy_if_hard()
 
     def run(self, n):
         """n more epochs.  Refuses to pass ``nepochs`` (the history has that many
@@ -416,11 +558,15 @@ class TrainLoop:
     def history(self):
         """train.py:114-122's arrays up to the current epoch (rows before
         ``start_epoch`` are 0): losses, objective, variances [epoch] and
-        completions [NT, epoch] (None without ``record_completions``)."""
+        completions [NT, epoch] (None without ``record_completions``); with
+        ``track_hard`` also hard_objective and hard_overtime (int32) [epoch]."""
         k = self.epoch
         bufs = dict(losses=self._losses[:k], objective=self._objective[:k],
                     variances=self._variances[:k],
                     completions=None if self._completions is None else self._completions[:, :k])
+        if self.track_hard:
+            bufs.update(hard_objective=self._hard_objective[:k],
+                        hard_overtime=self._hard_overtime[:k])
         return {n: None if t is None else t.cpu().numpy() for n, t in bufs.items()}
 
     def best(self):
@@ -430,6 +576,17 @@ class TrainLoop:
                     epoch=int(self._best_epoch), time=self._best_time.cpu().numpy(),
                     fiber_time=self._best_fiber_time.cpu().numpy(),
                     completion=self._best_completion.cpu().numpy())
+
+    def hard_best(self):
+        """The best integer objective so far (``track_hard``): utility, epoch
+        (-1: no epoch has had a positive hard utility) and the visits [E] (int32,
+        caller's edge order), fiber_time [NS], completion [NT] of that epoch."""
+        if not self.track_hard:
+            raise ValueError("hard_best() needs TrainLoop(..., track_hard=True)")
+        visits, fiber_time, completion = self._best_hard
+        return dict(utility=float(self._best_hard_utility), epoch=int(self._best_hard_epoch),
+                    visits=visits.cpu().numpy(), fiber_time=fiber_time.cpu().numpy(),
+                    completion=completion.cpu().numpy())
 
     def _optim_state(self, tensors):
         """optimizer.state_dict() with its state tensors replaced by

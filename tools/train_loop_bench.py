@@ -12,12 +12,18 @@
                which TrainLoop needs for the best state: (c) - (b') is what
                the three added launches and the device sharpness cost.
 
+  (c+h) loop+h (c) with ``track_hard=True`` (--track-hard): pfsgnn_schedule, the
+               hard history row and the second copy_if inside the replayed
+               graph; (c+h) - (c) is the epoch cost of tracking the integer
+               objective.
+
 Runs are interleaved (a, b, c, b', a, b, c, b', ...); each run times EPOCHS epochs
 between two device syncs; reported: the median over RUNS runs and their spread.
 Shapes: the reference's (1 x 2000 x 12, B = 3) and bench.py's (16 x 2394 x 128,
 B = 8).
 
     python tools/train_loop_bench.py [--shape ref|bench|both] [--runs 5] [--epochs 200]
+                                     [--track-hard]
 """
 import argparse
 import os
@@ -133,22 +139,25 @@ class Step:
 class Loop:
     """(c): TrainLoop."""
 
-    def __init__(self, shape, nepochs):
+    def __init__(self, shape, nepochs, track_hard=False):
         from pfsgnn.train import TrainLoop
         G, NF, NC, B = shape
         data, ci = make_batch(G, NF, NC)
         gnn, opt = make_model(NC, B, True)
-        self.loop = TrainLoop(gnn, opt, data, ci, nepochs, SHARPS, MIN_SHARP, PCLASS, PFIBER, seed=0)
+        self.loop = TrainLoop(gnn, opt, data, ci, nepochs, SHARPS, MIN_SHARP, PCLASS, PFIBER, seed=0,
+                              track_hard=track_hard)
         self.loop.run(2)            # the eager and the side-stream epoch, and the capture
 
     def run(self, n):
         self.loop.run(n)
 
 
-def measure(name, shape, runs, epochs):
+def measure(name, shape, runs, epochs, track_hard=False):
     nepochs = runs * epochs + 8
     variants = [("eager", Eager(shape, nepochs)), ("step", Step(shape, nepochs)),
                 ("loop", Loop(shape, nepochs)), ("step+t", Step(shape, nepochs, want_time=True))]
+    if track_hard:
+        variants.append(("loop+h", Loop(shape, nepochs, track_hard=True)))
     for _, v in variants:           # one untimed pass each
         v.run(3)
     torch.cuda.synchronize()
@@ -163,15 +172,24 @@ def measure(name, shape, runs, epochs):
     G, NF, NC, B = shape
     print(f"shape {name}: {G} x {NF} x {NC}, B = {B}; {runs} interleaved runs of {epochs} epochs, "
           f"ms per epoch")
-    med, tags = {}, {"eager": "a", "step": "b", "loop": "c", "step+t": "b'"}
+    med, tags = {}, {"eager": "a", "step": "b", "loop": "c", "step+t": "b'", "loop+h": "c+h"}
     for k, _ in variants:
         med[k] = statistics.median(ms[k])
-        print(f"  ({tags[k]:2s}) {k:6s} median {med[k]:8.4f}  min {min(ms[k]):8.4f}  "
+        print(f"  ({tags[k]:3s}) {k:6s} median {med[k]:8.4f}  min {min(ms[k]):8.4f}  "
               f"max {max(ms[k]):8.4f}  runs {' '.join(f'{x:.4f}' for x in ms[k])}")
     spread = max(ms["step"]) - min(ms["step"])
     print(f"  (c) - (b) = {1e3 * (med['loop'] - med['step']):8.2f} us per epoch; run-to-run spread "
           f"of (b) {1e3 * spread:.2f} us; (c) - (b') = {1e3 * (med['loop'] - med['step+t']):.2f} us; "
           f"(a) / (c) = {med['eager'] / med['loop']:.2f}x")
+    if track_hard:
+        hl = variants[4][1].loop
+        hh, hb = hl.history(), hl.hard_best()
+        assert np.isfinite(hh["hard_objective"]).all(), "TrainLoop's hard_objective is not finite"
+        print(f"  (c+h) - (c) = {1e3 * (med['loop+h'] - med['loop']):8.2f} us per epoch; run-to-run "
+              f"spread of (c) {1e3 * (max(ms['loop']) - min(ms['loop'])):.2f} us; hard objective "
+              f"{hh['hard_objective'][2:].min():.6g} .. {hh['hard_objective'][2:].max():.6g}, "
+              f"over-time fibers {hh['hard_overtime'][2:].min()} .. {hh['hard_overtime'][2:].max()}, "
+              f"best hard epoch {hb['epoch']} utility {hb['utility']:.6g}")
     hist = variants[2][1].loop
     b = hist.best()
     h = hist.history()
@@ -191,10 +209,12 @@ def main():
     ap.add_argument("--shape", default="both", choices=["ref", "bench", "both"])
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--epochs", type=int, default=200)
+    ap.add_argument("--track-hard", action="store_true",
+                    help="add (c+h): TrainLoop(track_hard=True), and report (c+h) - (c)")
     a = ap.parse_args()
     print(f"device {torch.cuda.get_device_name(0)}; torch {torch.__version__}")
     for name in (["ref", "bench"] if a.shape == "both" else [a.shape]):
-        measure(name, SHAPES[name], a.runs, a.epochs)
+        measure(name, SHAPES[name], a.runs, a.epochs, a.track_hard)
 
 
 if __name__ == "__main__":
