@@ -969,6 +969,86 @@ typedef struct pfsgnn_schedule_args {
 size_t pfsgnn_schedule_args_bytes(void);
 int pfsgnn_schedule(const pfsgnn_schedule_args* a, void* ws, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------- budgeted rounding
+ * pfsgnn_schedule_budget -- an integer schedule that fits every fiber's time.
+ * pfsgnn_schedule's floor (train.py:50, :74) never exceeds the allocation but
+ * drops every fractional visit; its round (np.round, train.py:256-257) puts
+ * fibers above total_time.  This op is largest-remainder apportionment per
+ * fiber: floor every edge, then give the fiber's remaining time to the edges
+ * with the largest fractional part while they still fit.  Edges are indexed by
+ * edge_index as in pfsgnn_schedule; T_e = ci[0][tgt_e].
+ *  1. Quotient.  time_e as pfsgnn_schedule computes it (EdgeTime on y, sc, sh,
+ *     times scale), or time_in[e] (caller's order) when time_in is set -- then
+ *     y, sc, sh and the decoder may be NULL.  v_e = time_e / T_e, one IEEE fp32
+ *     division; q_e = min(max(v_e, 0), 2^24).  A NaN quotient, or a T_e that is
+ *     not finite or <= 0, gives q_e = 0 and makes the edge INERT: 0 visits,
+ *     never a candidate, no fiber time.  quot [E] (optional, caller's order)
+ *     receives q_e.
+ *  2. Base.  base_e = (int32) floorf(q_e); frac_e = q_e - floorf(q_e), exact.
+ *  3. Per fiber, with ft = sum (double)visits_e * (double)T_e in double (every
+ *     product exact) and the key (frac_e, class, caller's edge position):
+ *     Down phase, only if ft > total_time after flooring: walk the edges in
+ *     ascending key order (smallest frac, then lower class, then lower
+ *     position); from each remove r = min(visits_e, k) visits, k the smallest
+ *     integer with ft - k T_e <= total_time (ceil of the double quotient, then
+ *     one exact step either way); stop once ft <= total_time.  An edge that
+ *     lost visits is REDUCED.
+ *     Up phase, every fiber: walk the edges that are neither inert nor reduced
+ *     in descending frac (ties: lower class, then lower position); an edge gets
+ *     +1 iff ft + T_e <= total_time (equality fits), ft updated after each
+ *     bump, at most one bump per edge.  A fiber that never enters the down
+ *     phase ends with every count in {floor, floor + 1}.
+ *  4. Outputs as pfsgnn_schedule's, by the same formulas (visits [E] int32 in
+ *     the caller's order, n_hard, completeness [G*NC], fiber_time [G*NF] the
+ *     fp32 sum of the fp32 products visits_e * T_e in a fixed order, utility,
+ *     over, worst [G]), and phase [G*NF] int32: bit 0 the fiber took the down
+ *     phase, bit 1 it got at least one bump, bit 2 it refused at least one
+ *     candidate for lack of time.
+ * Exactness contract.  When all the double sums above are exact, the result is
+ * a pure function of (q, edge_index, ci, total_time): identical for every edge
+ * order and layout, complete or sliced.  That holds for any class file whose T
+ * are multiples of 2^-20 below 2^20 (every shipped params file has integer T);
+ * then fiber_time's fp32 sum of integers is exact too and over = 0.  For other
+ * T the op is still bitwise reproducible run to run and every fiber satisfies
+ * ft <= total_time in the kernel's own double sum; a decision within one
+ * rounding of the budget may differ between layouts, and the fp32 fiber_time
+ * may round above total_time.
+ * Batch: as pfsgnn_schedule (complete with mode / perm, or sl + pos_user;
+ * repeated pairs of a general batch are separate edges, told apart by their
+ * position).  Fdim 8, 10, 16.  A complete batch's NC is bounded by the
+ * selection pass's LDS tile: pfsgnn_schedule_budget_max_nc() (>= 128).
+ * Workspace: pfsgnn_schedule_budget_ws_bytes(G, NF, NC, EP) bytes (EP: sl->EP,
+ * or 0 for a complete batch) -- one word per edge slot and the class partials;
+ * pfsgnn_workspace_bytes does not cover it for every shape.  Nothing
+ * allocates, synchronises or uses float atomics: capturable.
+ * Refused before any launch: a null struct, sl without pos_user or the
+ * reverse, sl with perm, mode outside 0..2, mode 0 without perm, Fdim outside
+ * 8 / 10 / 16, NC above pfsgnn_sliced_max_nc with sl or above
+ * pfsgnn_schedule_budget_max_nc without, a null output (quot may be NULL), a
+ * null ci, y or decoder NULL without time_in, a workspace too small.
+ * time_in without quot is allowed. */
+typedef struct pfsgnn_schedule_budget_args {
+  int G, NF, NC, F;
+  const pfsgnn_sliced_t* sl;
+  const int* pos_user;
+  int mode;
+  const int32_t* perm;
+  const float *y, *sc, *sh, *Wd1, *bd1, *Wd2, *bd2, *ci;
+  const float* time_in;
+  float scale, total_time, nfields;
+  int32_t *visits, *n_hard;
+  float *fiber_time, *completeness, *utility;
+  int32_t* over;
+  float* worst;
+  float* quot;
+  int32_t* phase;
+} pfsgnn_schedule_budget_args;
+size_t pfsgnn_schedule_budget_args_bytes(void);
+int pfsgnn_schedule_budget_max_nc(void);
+size_t pfsgnn_schedule_budget_ws_bytes(int G, int NF, int NC, long long EP);
+int pfsgnn_schedule_budget(const pfsgnn_schedule_budget_args* a, void* ws, size_t ws_bytes,
+                           void* stream);
+
 /* ---------------------------------------------------------------- training loop
  * The per-epoch bookkeeping of train.py:133-165 as three small launches, so a
  * whole epoch (these, the forward, the loss, the backward, pfsgnn_adam) is one

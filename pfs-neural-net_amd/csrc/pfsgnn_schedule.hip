@@ -348,3 +348,433 @@ extern "C" int pfsgnn_schedule(const pfsgnn_schedule_args* a, void* ws, size_t w
   }
   return pf::check_launch(where);
 }
+
+// ================================================================ budgeted rounding
+namespace {
+// pfsgnn_schedule_budget (include/pfsgnn.h): largest-remainder apportionment per
+// fiber.  Two launches and the finish above:
+//   1. the quotient pass (k_budget_quot / ksl_budget_quot: k_schedule's and
+//      ksl_schedule's loaders and ownership) writes one 32-bit word per edge in
+//      canonical or slot order -- the fp32 quotient q_e >= 0 (sign bit clear),
+//      or BQ_DONE | 0 for an inert edge or a padding slot -- and quot in the
+//      caller's order; with time_in there is no such launch, the selection
+//      pass gathers the times itself;
+//   2. the selection pass (k_budget_select / ksl_budget_select): a lane owns a
+//      fiber.  Dense: the 64 fibers' words staged as an LDS tile [NC][64];
+//      sliced: in place in the workspace (a fiber's steps are unbounded).  A
+//      word with the sign bit set is final (the count in its low 31 bits), any
+//      other is pending; each pick scans the fiber's words for the extreme
+//      pending key, decides, and writes the final word back, so no second
+//      per-edge state is needed.  The up phase scans only for candidates that
+//      still fit: ft only grows, so one that does not fit now never will -- one
+//      scan per bump, not one per candidate.
+// Budget arithmetic is double through __dadd_rn / __dmul_rn / __dsub_rn: no FMA
+// contraction.  (It would not matter for the products, which are exact in
+// double -- 24-bit count x 24-bit T -- but a contracted ft + k * T would round
+// once where the definition rounds twice when T is not on the 2^-20 grid.)
+constexpr int BUDGET_MAX_NC = 192;          // dense: (NC x 64 + NC) LDS words, 48.75 KB
+constexpr uint32_t BQ_DONE = 0x80000000u;
+
+__device__ __forceinline__ uint32_t budget_word(float time, float Ti, float* q_out) {
+  const float v = time / Ti;                 // one IEEE division
+  const bool inert = !(v == v) || !(Ti > 0.f) || !(Ti < INFINITY);
+  const float q = inert ? 0.f : (v > 0.f ? fminf(v, 16777216.f) : 0.f);
+  *q_out = q;
+  return inert ? BQ_DONE : __float_as_uint(q);
+}
+__device__ __forceinline__ int budget_final(uint32_t w) {
+  return (w & BQ_DONE) ? (int)(w & ~BQ_DONE) : (int)floorf(__uint_as_float(w));
+}
+
+template <int F>
+__global__ __launch_bounds__(256) void k_budget_quot(
+    EdgeGeo geo, const float* __restrict__ y, const float* __restrict__ sc,
+    const float* __restrict__ sh, const float* __restrict__ Wd1, const float* __restrict__ bd1,
+    const float* __restrict__ Wd2, const float* __restrict__ bd2, const float* __restrict__ ci,
+    float scale, int mode, const int32_t* __restrict__ perm, uint32_t* __restrict__ qws,
+    float* __restrict__ quot) {
+  EDGE_PROLOGUE
+  __shared__ __attribute__((aligned(16))) DecW<F> dw;
+  dw.load(Wd1, bd1, Wd2, bd2);
+  __syncthreads();
+  Y_PREFETCH_DECL(F)
+  CLASS_LOOP_BEGIN
+    float x[F];
+    Y_TAKE(F, x)
+    EdgeTime<F> L;
+    const float* dwp = dec_base(dw);
+    L.run(x, dwp, dwp + F * F, dwp + F * F + F, dwp + F * F + 2 * F, scale);
+    float q;
+    const uint32_t w = budget_word(L.time, ci[cn], &q);
+    if (fvalid) {
+      qws[e] = w;                            // canonical: consecutive fibers, coalesced
+      if (quot) {
+        const long long u = mode == 2 ? e : (mode == 1 ? eu : (long long)perm[e]);
+        quot[u] = q;
+      }
+    }
+  CLASS_LOOP_END
+}
+
+template <int F>
+__global__ __launch_bounds__(256) void ksl_budget_quot(
+    EdgeGeo geo, SlGeo sl, const int* __restrict__ pos_user, const float* __restrict__ y,
+    const float* __restrict__ sc, const float* __restrict__ sh, const float* __restrict__ Wd1,
+    const float* __restrict__ bd1, const float* __restrict__ Wd2, const float* __restrict__ bd2,
+    const float* __restrict__ ci, float scale, uint32_t* __restrict__ qws,
+    float* __restrict__ quot) {
+  SLL_PROLOGUE
+  (void)wave;
+  __shared__ __attribute__((aligned(16))) DecW<F> dw;
+  dw.load(Wd1, bd1, Wd2, bd2);
+  __syncthreads();
+  // (ksl_schedule's loader: the position opaque per iteration)
+  auto load = [&](int i) {
+    SlEdge<F> r;
+    r.in = k0 + 4 * i + q4 < k1;
+    long long p = p0 + 64ll * i;
+    asm volatile("" : "+v"(p));
+    r.cls = r.in ? (int)sl.cls[p] : 0xFF;
+    r.pos = r.in ? pos_user[p] : -1;
+    const float* yp = y + p;
+#pragma unroll
+    for (int k = 0; k < F; ++k) r.y[k] = r.in ? yp[(long long)k * EP] : 0.f;
+    return r;
+  };
+  SlEdge<F> cur = load(0);
+  for (int i = 0; i < nit; ++i) {
+    const SlEdge<F> nxt = load(i + 1);
+    SLL_STEP(cur)
+    float x[F];
+#pragma unroll
+    for (int k = 0; k < F; ++k) x[k] = sc ? fmaf(cur.y[k], sc[k], sh[k]) : cur.y[k];
+    EdgeTime<F> L;
+    const float* dwp = dec_base(dw);
+    L.run(x, dwp, dwp + F * F, dwp + F * F + F, dwp + F * F + 2 * F, scale);
+    float q;
+    const uint32_t w = budget_word(L.time, ci[cn], &q);
+    // every slot of the split is written: padding and fiber-less lanes as final 0
+    if (cur.in) qws[p0 + 64ll * i] = ev ? w : BQ_DONE;
+    if (ev && quot) quot[cur.pos] = q;
+    cur = nxt;
+  }
+}
+
+// the words of the lane's fiber: dense, column `lane` of the LDS tile (step k =
+// class k); sliced, the slots base + 16 k + j of the workspace, their class
+// bytes and caller positions
+struct DenseTile {
+  uint32_t* w;
+  int n;
+  __device__ __forceinline__ uint32_t get(int k) const { return w[k * 64]; }
+  __device__ __forceinline__ void put(int k, uint32_t v) const { w[k * 64] = v; }
+  __device__ __forceinline__ int cls(int k) const { return k; }
+  __device__ __forceinline__ int pos(int k) const { return k; }
+};
+struct SlicedTile {
+  uint32_t* w;
+  const uint8_t* c;
+  const int* p;
+  int n;
+  __device__ __forceinline__ uint32_t get(int k) const { return w[16 * k]; }
+  __device__ __forceinline__ void put(int k, uint32_t v) const { w[16 * k] = v; }
+  __device__ __forceinline__ int cls(int k) const { return c[16 * k]; }
+  __device__ __forceinline__ int pos(int k) const { return p[16 * k]; }
+};
+
+struct Pick {
+  int k, c;
+  float q;
+};
+// the pending edge with the extreme key (frac, class, caller position).  DOWN:
+// the smallest frac among those with a visit to lose.  Else the largest frac
+// among those that still fit, ft + T <= tot: ft only grows, so a candidate that
+// does not fit now never will, and the walk in descending key order would have
+// refused it -- skipping it here is the same walk with one scan per bump
+// instead of one per candidate; *unfit: a pending edge was passed over so.
+// Ties to the lower class, then the lower position.  k < 0: none
+template <bool DOWN, class Tile>
+__device__ __forceinline__ Pick budget_scan(const Tile& tl, int nmax, const float* Ts, double ft,
+                                            double tot, bool* unfit) {
+  Pick b{-1, 0, 0.f};
+  float bf = 0.f;
+  bool uf = false;
+  // branch-free per word (selects; the loads of an unrolled group issue
+  // together): a wave is alone on its SIMD here, nothing else hides a branchy
+  // body's LDS latency.  Only a (frac, class) tie -- a repeated pair -- branches
+#pragma unroll 4
+  for (int k = 0; k < nmax; ++k) {
+    const bool in = k < tl.n;
+    const uint32_t w = in ? tl.get(k) : BQ_DONE;
+    const bool pend = !(w & BQ_DONE);
+    const float q = __uint_as_float(w), fl = floorf(q), f = q - fl;   // exact in fp32
+    const int c = pend ? tl.cls(k) : 0;      // (a pending word has a class < NC)
+    bool cand;
+    if (DOWN) {
+      cand = pend && fl >= 1.f;
+    } else {
+      const bool fits = __dadd_rn(ft, (double)Ts[c]) <= tot;
+      cand = pend && fits;
+      uf |= pend && !fits;
+    }
+    bool better = b.k < 0 || (DOWN ? f < bf : f > bf) || (f == bf && c < b.c);
+    if (cand && !better && f == bf && c == b.c) better = tl.pos(k) < tl.pos(b.k);
+    const bool take = cand && better;
+    b.k = take ? k : b.k;
+    b.c = take ? c : b.c;
+    b.q = take ? q : b.q;
+    bf = take ? f : bf;
+  }
+  *unfit = uf;
+  return b;
+}
+
+// both phases on the lane's fiber; ft the double sum of floor(q) * T over its
+// pending edges.  -> the phase bits
+template <class Tile>
+__device__ __forceinline__ int budget_round_fiber(const Tile& tl, int nmax, const float* Ts,
+                                                  double ft, double tot) {
+  int ph = 0;
+  bool unfit = false;
+  if (ft > tot) {
+    ph |= 1;
+    while (ft > tot) {
+      const Pick b = budget_scan<true>(tl, nmax, Ts, ft, tot, &unfit);
+      if (b.k < 0) break;
+      const double Td = (double)Ts[b.c];
+      const int vis = (int)floorf(b.q);
+      // the smallest k with ft - k T <= tot: ceil of the quotient, then one
+      // exact step either way; beyond any count the edge is stripped
+      double kd = ceil(__dsub_rn(ft, tot) / Td);
+      if (!(kd < 33554432.0)) kd = 33554432.0;
+      if (kd >= 1.0 && __dsub_rn(ft, __dmul_rn(kd - 1.0, Td)) <= tot) kd -= 1.0;
+      else if (__dsub_rn(ft, __dmul_rn(kd, Td)) > tot) kd += 1.0;
+      const int r = kd < (double)vis ? (int)kd : vis;
+      ft = __dsub_rn(ft, __dmul_rn((double)r, Td));
+      tl.put(b.k, BQ_DONE | (uint32_t)(vis - r));
+    }
+  }
+  for (;;) {
+    unfit = false;
+    const Pick b = budget_scan<false>(tl, nmax, Ts, ft, tot, &unfit);
+    if (b.k < 0) break;                        // (what is left pending keeps its floor)
+    ft = __dadd_rn(ft, (double)Ts[b.c]);       // equality fits
+    ph |= 2;
+    tl.put(b.k, BQ_DONE | (uint32_t)((int)floorf(b.q) + 1));
+  }
+  return ph | (unfit ? 4 : 0);
+}
+
+// one wave per 64 fibers of a graph; dynamic LDS: Ts [NC rounded up to 64] |
+// tile [NC][64]
+__global__ __launch_bounds__(64) void k_budget_select(
+    int NF, int NC, int NFG, const uint32_t* __restrict__ qws, const float* __restrict__ time_in,
+    const float* __restrict__ ci, float total_time, int mode, const int32_t* __restrict__ perm,
+    int* __restrict__ visits, float* __restrict__ quot, float* __restrict__ fiber_time,
+    int* __restrict__ phase, int* __restrict__ part) {
+  extern __shared__ uint32_t budget_lds[];
+  const int lane = threadIdx.x, gg = blockIdx.x / NFG, fg = blockIdx.x % NFG;
+  float* Ts = reinterpret_cast<float*>(budget_lds);
+  for (int c = lane; c < NC; c += 64) Ts[c] = ci[(long long)gg * NC + c];
+  __syncthreads();
+  const int f = fg * 64 + lane;
+  const bool fvalid = f < NF;
+  const long long n = (long long)gg * NF + (fvalid ? f : 0);
+  // (a lane beyond NF holds final zeros: its column takes part in every walk)
+  const DenseTile tl{budget_lds + ((NC + 63) & ~63) + lane, NC};
+  const long long e0 = (long long)gg * NC * NF + (fvalid ? f : 0);
+  auto user = [&](int k) {
+    const long long e = e0 + (long long)k * NF;
+    return mode == 2 ? e : (mode == 1 ? n * NC + k : (long long)perm[e]);
+  };
+  double ft = 0.0;
+  if (time_in) {
+    for (int k = 0; k < NC; ++k) {
+      const long long u = user(k);
+      float q;
+      const uint32_t w = budget_word(time_in[u], Ts[k], &q);
+      if (fvalid && quot) quot[u] = q;
+      tl.put(k, fvalid ? w : BQ_DONE);
+    }
+  } else {
+    // canonical words: consecutive fibers; unconditional loads (a lane beyond NF
+    // re-reads fiber 0's), so that an unrolled group's loads are in flight together
+#pragma unroll 8
+    for (int k = 0; k < NC; ++k) tl.put(k, fvalid ? qws[e0 + (long long)k * NF] : BQ_DONE);
+  }
+#pragma unroll 4
+  for (int k = 0; k < NC; ++k) {
+    const uint32_t w = tl.get(k);
+    const double t = __dmul_rn((double)floorf(__uint_as_float(w)), (double)Ts[k]);
+    ft = (w & BQ_DONE) ? ft : __dadd_rn(ft, t);
+  }
+  const int ph = budget_round_fiber(tl, NC, Ts, ft, (double)total_time);
+  // counts out in class order: the class partial of the 64 fibers, the fp32
+  // fiber time (fp32 products, ascending class)
+  float ft32 = 0.f;
+  for (int k = 0; k < NC; ++k) {
+    const int v = fvalid ? budget_final(tl.get(k)) : 0;
+    if (fvalid) {
+      visits[user(k)] = v;
+      if (v) ft32 = __fadd_rn(ft32, __fmul_rn((float)v, Ts[k]));
+    }
+    const int ns = wave_isum(v);
+    if (lane == 0) part[((size_t)gg * NFG + fg) * NC + k] = ns;
+  }
+  if (fvalid) {
+    fiber_time[n] = ft32;
+    phase[n] = ph;
+  }
+}
+
+// one wave per group of 4 slices (64 fiber lanes of a graph)
+__global__ __launch_bounds__(64) void ksl_budget_select(
+    SlGeo sl, int NC, int NFG, const int* __restrict__ pos_user, uint32_t* qws,
+    const float* __restrict__ time_in, const float* __restrict__ ci, float total_time,
+    int* __restrict__ visits, float* __restrict__ quot, float* __restrict__ fiber_time,
+    int* __restrict__ phase, int* __restrict__ part) {
+  __shared__ float Ts[MAXC];
+  __shared__ int cnt[MAXC];
+  const int lane = threadIdx.x, grp = blockIdx.x, gg = grp / NFG;
+  for (int c = lane; c < MAXC; c += 64) {
+    Ts[c] = c < NC ? ci[(long long)gg * NC + c] : 0.f;
+    cnt[c] = 0;
+  }
+  __syncthreads();
+  const int slc = 4 * grp + (lane >> 4), j = lane & 15;
+  const int fib = sl.fib[slc * 16 + j];
+  const long long pb = (long long)sl.base[slc] + j;
+  const int n = fib >= 0 ? sl.len[slc] : 0;
+  int nmax = n;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) nmax = max(nmax, __shfl_xor(nmax, o));
+  const SlicedTile tl{qws + pb, sl.cls + pb, pos_user + pb, n};
+  double ft = 0.0;
+  for (int k = 0; k < nmax; ++k) {
+    if (k >= n) continue;
+    uint32_t w;
+    if (time_in) {
+      const int c = tl.cls(k), p = tl.pos(k);
+      w = BQ_DONE;
+      if (c < NC && p >= 0) {
+        float q;
+        w = budget_word(time_in[p], Ts[c], &q);
+        if (quot) quot[p] = q;
+      }
+      tl.put(k, w);
+    } else {
+      w = tl.get(k);
+    }
+    if (!(w & BQ_DONE))
+      ft = __dadd_rn(ft, __dmul_rn((double)floorf(__uint_as_float(w)), (double)Ts[tl.cls(k)]));
+  }
+  const int ph = budget_round_fiber(tl, nmax, Ts, ft, (double)total_time);
+  float ft32 = 0.f;
+  for (int k = 0; k < nmax; ++k) {
+    if (k >= n) continue;
+    const int c = tl.cls(k), p = tl.pos(k);
+    if (c >= NC || p < 0) continue;
+    const int v = budget_final(tl.get(k));
+    visits[p] = v;
+    if (v) {
+      ft32 = __fadd_rn(ft32, __fmul_rn((float)v, Ts[c]));
+      atomicAdd(&cnt[c], v);                 // LDS integer add: order-free
+    }
+  }
+  if (fib >= 0) {
+    fiber_time[fib] = ft32;
+    phase[fib] = ph;
+  }
+  __syncthreads();
+  for (int c = lane; c < NC; c += 64) part[(size_t)grp * NC + c] = cnt[c];
+}
+
+size_t budget_ws_bytes(long long slots, int G, int NF, int NC) {
+  const size_t NFG = (NF + 63) / 64;
+  return align256((size_t)slots * sizeof(uint32_t)) + align256((size_t)G * NFG * NC * sizeof(int));
+}
+
+}  // namespace
+
+extern "C" size_t pfsgnn_schedule_budget_args_bytes(void) {
+  return sizeof(pfsgnn_schedule_budget_args);
+}
+extern "C" int pfsgnn_schedule_budget_max_nc(void) { return BUDGET_MAX_NC; }
+extern "C" size_t pfsgnn_schedule_budget_ws_bytes(int G, int NF, int NC, long long EP) {
+  if (G <= 0 || NF <= 0 || NC <= 0) return 0;
+  return budget_ws_bytes(EP > 0 ? EP : (long long)G * NF * NC, G, NF, NC);
+}
+
+extern "C" int pfsgnn_schedule_budget(const pfsgnn_schedule_budget_args* a, void* ws,
+                                      size_t ws_bytes, void* stream) {
+  const char* where = "pfsgnn_schedule_budget";
+  PF_REQUIRE(a, where, "null argument struct");
+  PF_REQUIRE(!a->sl == !a->pos_user, where,
+             "sl and pos_user go together (both set: a sliced general batch; both NULL: complete)");
+  PF_REQUIRE(!(a->sl && a->perm), where,
+             "sl with perm: a sliced batch maps its edges by pos_user, mode and perm are the "
+             "complete batch's");
+  PF_REQUIRE(a->sl || (a->mode >= 0 && a->mode <= 2), where, "mode must be 0 (perm), 1 or 2");
+  PF_REQUIRE(a->sl || a->mode != 0 || a->perm, where, "mode 0 needs perm");
+  const int G = a->G, NF = a->NF, NC = a->NC, F = a->F;
+  PF_REQUIRE(F == 8 || F == 10 || F == 16, where, "unsupported Fdim (8, 10, 16)");
+  PF_REQUIRE(G > 0 && NF > 0 && NC > 0, where, "need G > 0, NF > 0, NC > 0");
+  if (a->sl) {
+    const pfsgnn_sliced_t* s = a->sl;
+    PF_REQUIRE(s->fib && s->base && s->len && s->cls && s->EP > 0 && s->E > 0 && s->EP >= s->E,
+               where, "bad sliced layout");
+    int m = 0;
+    if (pfsgnn_sliced_max_nc(F, &m) != 0 || m <= 0)
+      return pf::fail(where, "sliced layout: the current edge path has no sliced kernels");
+    PF_REQUIRE(NC <= m && NC <= MAXC, where,
+               "sliced layout: too many classes per graph (pfsgnn_sliced_max_nc)");
+    PF_REQUIRE(s->EP < (1ll << 31), where, "EP too large for int32 slot ids");
+  } else {
+    PF_REQUIRE(NC <= BUDGET_MAX_NC, where,
+               "too many classes per graph for the selection pass's LDS tile "
+               "(pfsgnn_schedule_budget_max_nc)");
+    PF_REQUIRE((long long)G * NF * NC < (1ll << 31), where, "E too large for int32 edge ids");
+  }
+  PF_REQUIRE(a->visits && a->n_hard && a->fiber_time && a->completeness && a->utility && a->over &&
+                 a->worst && a->phase,
+             where, "null output");
+  PF_REQUIRE(a->ci && (a->time_in || (a->y && a->Wd1 && a->bd1 && a->Wd2 && a->bd2 &&
+                                      (!a->sc == !a->sh))),
+             where, "null input (without time_in: y and the decoder; sc and sh go together)");
+  hipStream_t st = as_stream(stream);
+  Ws w{reinterpret_cast<char*>(ws), ws_bytes};
+  const int NFG = (NF + 63) / 64;
+  const long long slots = a->sl ? a->sl->EP : (long long)G * NF * NC;
+  uint32_t* qws = static_cast<uint32_t*>(w.take((size_t)slots * sizeof(uint32_t)));
+  int* part = static_cast<int*>(w.take((size_t)G * NFG * NC * sizeof(int)));
+  PF_REQUIRE(qws && part, where, "workspace too small (pfsgnn_schedule_budget_ws_bytes)");
+  if (a->sl) {
+    const pfsgnn_sliced_t& s = *a->sl;
+    const SlGeo sg{s.fib, s.base, s.len, s.cls, s.pco, s.EP, s.E, s.maxdeg};
+    if (!a->time_in) {
+      const EdgeGeo geo = pfm::sl_geo(G, NF, NC, sg);
+      LOSS_DISPATCH_F(F, hipLaunchKernelGGL(ksl_budget_quot<FF>, dim3(geo.nblocks), dim3(256), 0, st,
+                                            geo, sg, a->pos_user, a->y, a->sc, a->sh, a->Wd1, a->bd1,
+                                            a->Wd2, a->bd2, a->ci, a->scale, qws, a->quot));
+    }
+    hipLaunchKernelGGL(ksl_budget_select, dim3(G * NFG), dim3(64), 0, st, sg, NC, NFG, a->pos_user,
+                       qws, a->time_in, a->ci, a->total_time, a->visits, a->quot, a->fiber_time,
+                       a->phase, part);
+  } else {
+    if (!a->time_in) {
+      const EdgeGeo geo = loss_geo(G, NF, NC);
+      LOSS_DISPATCH_F(F, hipLaunchKernelGGL(k_budget_quot<FF>, dim3(edge_grid(geo)), dim3(256), 0, st,
+                                            geo, a->y, a->sc, a->sh, a->Wd1, a->bd1, a->Wd2, a->bd2,
+                                            a->ci, a->scale, a->mode, a->perm, qws, a->quot));
+    }
+    const size_t lds = ((size_t)((NC + 63) & ~63) + (size_t)NC * 64) * sizeof(uint32_t);
+    hipLaunchKernelGGL(k_budget_select, dim3(G * NFG), dim3(64), lds, st, NF, NC, NFG, qws,
+                       a->time_in, a->ci, a->total_time, a->mode, a->perm, a->visits, a->quot,
+                       a->fiber_time, a->phase, part);
+  }
+  // the selection pass owns whole fibers: one fiber-time row, NFG class partial rows
+  hipLaunchKernelGGL(k_schedule_finish, dim3(G), dim3(256), 0, st, NF, NC, G * NC, NFG, 1,
+                     (long long)G * NF, part, a->fiber_time, a->ci, a->total_time, a->nfields,
+                     a->n_hard, a->fiber_time, a->completeness, a->utility, a->over, a->worst);
+  return pf::check_launch(where);
+}

@@ -230,6 +230,17 @@ class ScheduleArgs(ctypes.Structure):
                         "worst"))
 
 
+class ScheduleBudgetArgs(ctypes.Structure):
+    """pfsgnn_schedule_budget_args: budgeted rounding (largest remainder per
+    fiber) of a complete (mode, perm) or sliced (sl + pos_user) batch."""
+    _fields_ = ([("G", I), ("NF", I), ("NC", I), ("F", I), ("sl", SLP)]
+                + _ptrs("pos_user") + [("mode", I)]
+                + _ptrs("perm", "y", "sc", "sh", "Wd1", "bd1", "Wd2", "bd2", "ci", "time_in")
+                + [("scale", FL), ("total_time", FL), ("nfields", FL)]
+                + _ptrs("visits", "n_hard", "fiber_time", "completeness", "utility", "over",
+                        "worst", "quot", "phase"))
+
+
 class CopyJob(ctypes.Structure):
     """pfsgnn_copy_job: n 4-byte words from src to dst."""
     _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("n", LL)]
@@ -353,6 +364,10 @@ _SIGS = {
     "pfsgnn_schedule": ([ctypes.POINTER(ScheduleArgs), P, SZ, P], I),
     "pfsgnn_train_record_hard_args_bytes": ([], SZ),
     "pfsgnn_train_record_hard": ([ctypes.POINTER(TrainRecordHardArgs), P], I),
+    "pfsgnn_schedule_budget_args_bytes": ([], SZ),
+    "pfsgnn_schedule_budget_max_nc": ([], I),
+    "pfsgnn_schedule_budget_ws_bytes": ([I, I, I, LL], SZ),
+    "pfsgnn_schedule_budget": ([ctypes.POINTER(ScheduleBudgetArgs), P, SZ, P], I),
 }
 for _op, _cls in EDGE_ARGS.items():
     _SIGS["pfsgnn_" + _op] = ([ctypes.POINTER(_cls), P, SZ, P], I)
@@ -380,14 +395,20 @@ def lib():
                 f"{_LIB_PATH} is {L.pfsgnn_version().decode()!r}, this binding is for "
                 f"{ABI_VERSION!r}: rebuild it with `make -C pfs-neural-net_amd`")
         for name, (args, ret) in _SIGS.items():
-            fn = getattr(L, name)
+            # (a library of this version built before an entry point was added)
+            fn = getattr(L, name, None)
+            if fn is None:
+                raise NativeUnavailable(
+                    f"{_LIB_PATH} does not export {name}: it was built from older sources; "
+                    "rebuild it with `make -C pfs-neural-net_amd`")
             fn.argtypes = args
             fn.restype = ret
         sizes = [("pfsgnn_loss_args_bytes", (), LossArgs),
                  ("pfsgnn_train_record_args_bytes", (), TrainRecordArgs)]
         sizes += [("pfsgnn_edge_args_bytes", (op,), cls) for op, cls in enumerate(EDGE_ARGS.values())]
         sizes += [("pfsgnn_train_record_hard_args_bytes", (), TrainRecordHardArgs),
-                  ("pfsgnn_schedule_args_bytes", (), ScheduleArgs)]
+                  ("pfsgnn_schedule_args_bytes", (), ScheduleArgs),
+                  ("pfsgnn_schedule_budget_args_bytes", (), ScheduleBudgetArgs)]
         for query, qargs, cls in sizes:
             got, call = getattr(L, query)(*qargs), f"{query}({', '.join(map(str, qargs))})"
             if got != ctypes.sizeof(cls):
@@ -583,17 +604,19 @@ class HipBackend:
     def ones(self, *shape):
         return torch.ones(*shape, dtype=torch.float32, device=self.device)
 
-    def workspace(self, d=None):
+    def workspace(self, d=None, extra=0):
+        """``extra``: bytes an op needs beyond pfsgnn_workspace_bytes' promise
+        (pfsgnn_schedule_budget_ws_bytes)."""
         need = lib().pfsgnn_workspace_bytes(d.G, d.NF, d.NC, d.F) if d is not None else 0
-        need = max(need, 16 << 20)
+        need = max(need, 16 << 20, int(extra))
         if self._ws is None or self._ws.numel() < need:
             if self._ws is not None:
                 self._retired.append(self._ws)
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         return self._ws
 
-    def _wsargs(self, d=None):
-        ws = self.workspace(d)
+    def _wsargs(self, d=None, extra=0):
+        ws = self.workspace(d, extra)
         return ws.data_ptr(), ws.numel()
 
     @staticmethod
@@ -1632,6 +1655,55 @@ class HipBackend:
             setattr(a, k, v.data_ptr())
         ws, wsb = self._wsargs(d)
         _call("pfsgnn_schedule", ctypes.byref(a), ws, wsb, _stream())
+        return out
+
+    def schedule_budget_max_nc(self):
+        """The most classes per graph of a complete batch (pfsgnn_schedule_budget_max_nc)."""
+        return int(lib().pfsgnn_schedule_budget_max_nc())
+
+    def schedule_budget(self, d, y, sc, sh, Wd1, bd1, Wd2, bd2, ci, scale, total_time, nfields,
+                        mode=1, perm=None, time_in=None, out=None):
+        """Budgeted rounding of the lazy edge state, or of ``time_in`` [E] (the
+        caller's edge order; then y, sc, sh and the decoder may be None)
+        (pfsgnn_schedule_budget) -> ``schedule``'s seven tensors, then quot [E]
+        (the fp32 quotient that was rounded, caller's order) and phase [NS] int32
+        (bit 0: down phase, 1: bumped, 2: refused a candidate).  ``out``: the nine
+        tensors to write into."""
+        sl = self._loss_layout(d)
+        i32 = dict(dtype=torch.int32, device=self.device)
+        if out is None:
+            out = (torch.empty(d.E, **i32), torch.empty(d.NT, **i32), self.empty(d.NS),
+                   self.empty(d.NT), self.empty(d.G), torch.empty(d.G, **i32), self.empty(d.G),
+                   self.empty(d.E), torch.empty(d.NS, **i32))
+        visits, n_hard, fiber_time, comp, utility, over, worst, quot, phase = out
+        assert visits.dtype == n_hard.dtype == over.dtype == phase.dtype == torch.int32
+        self._chk(y, sc, sh, Wd1, bd1, Wd2, bd2, time_in, fiber_time, comp, utility, worst, quot)
+        assert all(t.is_cuda and t.is_contiguous() for t in (visits, n_hard, over, phase))
+        assert visits.numel() == quot.numel() == d.E and n_hard.numel() == comp.numel() == d.NT
+        assert fiber_time.numel() == phase.numel() == d.NS
+        assert min(utility.numel(), over.numel(), worst.numel()) == d.G
+        assert time_in is not None or tuple(y.shape) == (d.F, d.EP), (d.F, d.EP)
+        assert time_in is None or time_in.numel() == d.E
+        ci = ci.contiguous()
+        assert ci.numel() >= 2 * d.NT
+        a = ScheduleBudgetArgs(G=d.G, NF=d.NF, NC=d.NC, F=d.F)
+        if sl is not None:
+            a.sl, a.pos_user = sl.ref, sl.pos_user.data_ptr()
+        else:
+            a.mode = int(mode)
+            if perm is not None:
+                assert perm.dtype == torch.int32 and perm.is_cuda and perm.numel() == d.E
+                a.perm = perm.data_ptr()
+        for k, v in dict(y=y, sc=sc, sh=sh, Wd1=Wd1, bd1=bd1, Wd2=Wd2, bd2=bd2, ci=ci,
+                         time_in=time_in).items():
+            setattr(a, k, _ptr(v))
+        a.scale, a.total_time, a.nfields = float(scale), float(total_time), float(nfields)
+        for k, v in zip(("visits", "n_hard", "fiber_time", "completeness", "utility", "over",
+                         "worst", "quot", "phase"), out):
+            setattr(a, k, v.data_ptr())
+        need = lib().pfsgnn_schedule_budget_ws_bytes(d.G, d.NF, d.NC, 0 if sl is None else sl.EP)
+        ws, wsb = self._wsargs(d, need)
+        _call("pfsgnn_schedule_budget", ctypes.byref(a), ws, wsb, _stream())
         return out
 
     def loss_finalize(self, d, n_prime, fiber_time, tvar, ci, pclass, pfiber, total_time, nfields,

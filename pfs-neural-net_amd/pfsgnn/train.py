@@ -204,10 +204,13 @@ def _loss_apply(graph, class_info, pclass, pfiber, sharpness, want_time, gnn, se
 HardSchedule = collections.namedtuple(
     "HardSchedule", "visits n fiber_time completeness utility over worst")
 
+BudgetSchedule = collections.namedtuple(
+    "BudgetSchedule", HardSchedule._fields + ("quot", "phase"))
+
 _ROUNDINGS = {"floor": 0, "round": 1}
 
 
-def hard_schedule(graph, class_info, rounding="floor", *, gnn=None):
+def hard_schedule(graph, class_info, rounding="floor", *, gnn=None, time=None):
     """The integer evaluation of an allocation: whole visits per edge and what
     follows from them -- train.py:50's commented ``scatter(torch.floor(visited),
     tgt)``, the "hard counts & diagnostics" of train.py:74, and, with
@@ -225,13 +228,83 @@ def hard_schedule(graph, class_info, rounding="floor", *, gnn=None):
     accepted (there is no positional noise counter), and sliced general
     batches; ``visits`` [E] is in the caller's edge order.  The fused op
     (pfsgnn_schedule) reads the lazy final edge state: ``out.x_e`` is not
-    materialised.  Returns a ``HardSchedule`` of device tensors without grad."""
-    return _hard_schedule(graph, class_info, rounding, gnn, None)
+    materialised.  Returns a ``HardSchedule`` of device tensors without grad.
+
+    ``rounding="budget"`` is the rounding a user can execute: floor every edge,
+    then give each fiber's remaining time to the edges with the largest
+    fractional part while they still fit TOTAL_TIME (largest remainder; a fiber
+    whose floor alone is over loses visits from the smallest fractional parts
+    first) -- the definition is pfsgnn_schedule_budget's in include/pfsgnn.h.
+    It returns a ``BudgetSchedule``: ``HardSchedule``'s fields, ``quot`` [E]
+    (the fp32 quotient that was rounded) and ``phase`` [NS] (int32; bit 0 the
+    fiber took the down phase, bit 1 it got a bump, bit 2 it refused a
+    candidate).  ``time`` [E] (budget rounding only; the caller's edge order,
+    e.g. ``TrainLoop.best()["time"]``) is rounded in place of the graph's own
+    edge times."""
+    return _hard_schedule(graph, class_info, rounding, gnn, None, time)
 
 
-def _hard_schedule(graph, class_info, rounding, gnn, out):
-    if rounding not in _ROUNDINGS:
-        raise ValueError(f"rounding must be 'floor' or 'round'; got {rounding!r}")
+def _budget_round_host(q, inert, src, tgt, T, total_time, NS):
+    """pfsgnn_schedule_budget's steps 2-3 on the host, for backends without the
+    op: each fiber's edges sorted once by key, one pass per phase.  ``q`` fp32
+    [E], ``T`` fp32 [NT] -> (visits int32 [E], phase int32 [NS])."""
+    q = q.cpu().numpy().astype(np.float32)
+    inert = inert.cpu().numpy()
+    src, tgt = src.cpu().numpy(), tgt.cpu().numpy()
+    Td = T.cpu().numpy().astype(np.float64)[tgt]
+    base = np.floor(q)
+    frac = q - base
+    vis = base.astype(np.int64)
+    pos = np.arange(q.size)
+    asc = np.lexsort((pos, tgt, frac))
+    desc = np.lexsort((pos, tgt, -frac))
+    asc = asc[np.argsort(src[asc], kind="stable")]
+    desc = desc[np.argsort(src[desc], kind="stable")]
+    lo = np.searchsorted(src[asc], np.arange(NS + 1))
+    phase = np.zeros(NS, np.int32)
+    total = float(np.float32(total_time))
+    for f in range(NS):
+        ea, ed = asc[lo[f]:lo[f + 1]], desc[lo[f]:lo[f + 1]]
+        ft = 0.0
+        for e in ea:
+            if vis[e]:                       # (an inert edge: 0 visits, whatever its T)
+                ft += float(vis[e]) * Td[e]
+        cand = ~inert[ea]
+        cand = dict(zip(ea.tolist(), cand.tolist()))
+        if ft > total:
+            phase[f] |= 1
+            for e in ea:
+                if ft <= total:
+                    break
+                if vis[e] == 0:
+                    continue
+                k = float(np.ceil((ft - total) / Td[e]))
+                if k >= 1 and ft - (k - 1) * Td[e] <= total:
+                    k -= 1
+                elif ft - k * Td[e] > total:
+                    k += 1
+                r = int(min(float(vis[e]), k))
+                ft -= r * Td[e]
+                vis[e] -= r
+                cand[e] = False
+        for e in ed:
+            if not cand[e]:
+                continue
+            if ft + Td[e] <= total:
+                ft += Td[e]
+                vis[e] += 1
+                phase[f] |= 2
+            else:
+                phase[f] |= 4
+    return torch.from_numpy(vis.astype(np.int32)), torch.from_numpy(phase)
+
+
+def _hard_schedule(graph, class_info, rounding, gnn, out, time=None):
+    budget = rounding == "budget"
+    if not budget and rounding not in _ROUNDINGS:
+        raise ValueError(f"rounding must be 'floor', 'round' or 'budget'; got {rounding!r}")
+    if time is not None and not budget:
+        raise ValueError("time= is budget rounding only (rounding='budget')")
     pf = graph.__dict__.get("_pf")
     if pf is None or graph.__dict__.get("_pf_replaced"):
         raise NotImplementedError("hard_schedule needs the BipartiteData returned by "
@@ -251,7 +324,19 @@ def _hard_schedule(graph, class_info, rounding, gnn, out):
     ci = _class_info_cm(class_info, d)
     be = backend()
     scale = float(config.TOTAL_TIME) / d.NC
-    if hasattr(be, "schedule"):
+    if time is not None:
+        time = torch.as_tensor(time, dtype=be.dtype, device=ci.device).reshape(-1).contiguous()
+        if time.numel() != d.E:
+            raise ValueError(f"time has {time.numel()} entries for {d.E} edges")
+    if budget and hasattr(be, "schedule_budget"):
+        P = model._flat_params()
+        y, sc, sh = (None, None, None) if time is not None else xe3
+        res = be.schedule_budget(d, y, sc, sh, P["decoder_e.0.weight"], P["decoder_e.0.bias"],
+                                 P["decoder_e.2.weight"], P["decoder_e.2.bias"], ci, scale,
+                                 float(config.TOTAL_TIME), float(config.NFIELDS), mode=lay.mode,
+                                 perm=lay.perm, time_in=time, out=out)
+        return BudgetSchedule(*res)
+    if not budget and hasattr(be, "schedule"):
         P = model._flat_params()
         y, sc, sh = xe3
         res = be.schedule(d, y, sc, sh, P["decoder_e.0.weight"], P["decoder_e.0.bias"],
@@ -262,22 +347,34 @@ def _hard_schedule(graph, class_info, rounding, gnn, out):
     # a backend without the op (a CPU emulation of the op set): torch restatement
     with torch.no_grad():
         src, tgt = graph.edge_index[0], graph.edge_index[1]
-        time = model.edge_prediction(graph.x_e.detach(), scale=scale).reshape(-1)
+        if time is None:
+            time = model.edge_prediction(graph.x_e.detach(), scale=scale).reshape(-1)
         T = ci[0][tgt]
         v = time / T
-        visits = (torch.floor(v) if rounding == "floor" else torch.round(v)).to(torch.int32)
+        extra = ()
+        if budget:
+            inert = torch.isnan(v) | ~(T > 0) | ~torch.isfinite(T)
+            quot = torch.where(inert, torch.zeros_like(v), v.clamp(0.0, 2.0 ** 24))
+            visits, phase = _budget_round_host(quot, inert, src, tgt, ci[0], config.TOTAL_TIME,
+                                               d.NS)
+            visits, phase = visits.to(v.device), phase.to(v.device)
+            Tz = torch.where(inert, torch.zeros_like(T), T)
+            extra = (quot, phase)
+        else:
+            visits = (torch.floor(v) if rounding == "floor" else torch.round(v)).to(torch.int32)
+            Tz = T
         n = torch.zeros(d.NT, dtype=torch.int32, device=v.device).index_add_(0, tgt, visits)
         ft = torch.zeros(d.NS, dtype=v.dtype, device=v.device).index_add_(
-            0, src, visits.to(v.dtype) * T)
+            0, src, visits.to(v.dtype) * Tz)
         comp = n.to(v.dtype) / (ci[1] / config.NFIELDS)
         res = (visits, n, ft, comp, comp.view(d.G, d.NC).min(dim=1).values,
                (ft.view(d.G, d.NF) > config.TOTAL_TIME).sum(dim=1).to(torch.int32),
-               ft.view(d.G, d.NF).max(dim=1).values)
+               ft.view(d.G, d.NF).max(dim=1).values) + extra
         if out is not None:
             for o, r in zip(out, res):
                 o.copy_(r)
             res = out
-    return HardSchedule(*res)
+    return (BudgetSchedule if budget else HardSchedule)(*res)
 
 
 # ---------------------------------------------------------------- training
@@ -325,6 +422,10 @@ class TrainLoop:
     epoch's visits, fiber_time and completion (``hard_best()``).  No parameter
     snapshot is kept for it: the checkpoint criterion stays the soft one.  With
     the default False the step issues exactly the launches listed above.
+    ``track_hard="budget"`` tracks the best *executable* schedule instead: the
+    same rows and best state from ``hard_schedule(..., "budget")``
+    (pfsgnn_schedule_budget: every fiber within TOTAL_TIME, so ``hard_overtime``
+    stays 0); ``True`` and ``"floor"`` are the floor path, launch for launch.
 
     One divergence from the reference: it rewrites the checkpoint file on every
     improvement; here the best state stays on the device until asked for.
@@ -379,11 +480,17 @@ class TrainLoop:
         self._jobs = self._snap = None
         self._graph, self._warm = None, 0
         # the integer objective (hard_schedule's outputs, its history and best state)
+        if track_hard not in (False, True, "floor", "budget"):
+            raise ValueError(f"track_hard must be False, True, 'floor' or 'budget'; got "
+                             f"{track_hard!r}")
         self.track_hard = bool(track_hard)
+        self._hard_rounding = "budget" if track_hard == "budget" else "floor"
         if self.track_hard:
             i32 = torch.int32
             self._hard = HardSchedule(buf(E, dtype=i32), buf(NT, dtype=i32), buf(NS), buf(NT),
                                       buf(G), buf(G, dtype=i32), buf(G))
+            if self._hard_rounding == "budget":
+                self._hard = BudgetSchedule(*self._hard, buf(E), buf(NS, dtype=i32))
             self._hard_objective, self._hard_overtime = buf(nepochs), buf(nepochs, dtype=i32)
             self._improved_hard, self._best_hard_utility = buf(1, dtype=i32), buf(1)
             self._best_hard_epoch = buf(1, dtype=torch.int64, fill=-1)
@@ -441,10 +548,10 @@ class TrainLoop:
                 t.copy_(s.detach())
 
     def _record_hard(self, out):
-        """The epoch's integer objective (floor) into the preallocated buffers,
-        its history rows and best-tracking."""
+        """The epoch's integer objective (floor, or the budgeted rounding) into
+        the preallocated buffers, its history rows and best-tracking."""
         be = self._be
-        hs = _hard_schedule(out, self.class_info, "floor", None, self._hard)
+        hs = _hard_schedule(out, self.class_info, self._hard_rounding, None, self._hard)
         if hasattr(be, "train_record_hard"):
             d = out.__dict__["_pf"][1]
             be.train_record_hard(d, self.nepochs, self._epoch, hs.utility, hs.over,

@@ -16,6 +16,10 @@
                hard history row and the second copy_if inside the replayed
                graph; (c+h) - (c) is the epoch cost of tracking the integer
                objective.
+  (c+b) loop+b (c) with ``track_hard="budget"`` (--track-hard budget, beside
+               (c+h)): pfsgnn_schedule_budget in place of pfsgnn_schedule --
+               the best *executable* schedule; (c+b) - (c+h) is what the
+               selection pass adds to the floor evaluation.
 
 Runs are interleaved (a, b, c, b', a, b, c, b', ...); each run times EPOCHS epochs
 between two device syncs; reported: the median over RUNS runs and their spread.
@@ -23,7 +27,7 @@ Shapes: the reference's (1 x 2000 x 12, B = 3) and bench.py's (16 x 2394 x 128,
 B = 8).
 
     python tools/train_loop_bench.py [--shape ref|bench|both] [--runs 5] [--epochs 200]
-                                     [--track-hard]
+                                     [--track-hard [floor|budget]]
 """
 import argparse
 import os
@@ -158,6 +162,8 @@ def measure(name, shape, runs, epochs, track_hard=False):
                 ("loop", Loop(shape, nepochs)), ("step+t", Step(shape, nepochs, want_time=True))]
     if track_hard:
         variants.append(("loop+h", Loop(shape, nepochs, track_hard=True)))
+    if track_hard == "budget":
+        variants.append(("loop+b", Loop(shape, nepochs, track_hard="budget")))
     for _, v in variants:           # one untimed pass each
         v.run(3)
     torch.cuda.synchronize()
@@ -172,7 +178,8 @@ def measure(name, shape, runs, epochs, track_hard=False):
     G, NF, NC, B = shape
     print(f"shape {name}: {G} x {NF} x {NC}, B = {B}; {runs} interleaved runs of {epochs} epochs, "
           f"ms per epoch")
-    med, tags = {}, {"eager": "a", "step": "b", "loop": "c", "step+t": "b'", "loop+h": "c+h"}
+    med, tags = {}, {"eager": "a", "step": "b", "loop": "c", "step+t": "b'", "loop+h": "c+h",
+                 "loop+b": "c+b"}
     for k, _ in variants:
         med[k] = statistics.median(ms[k])
         print(f"  ({tags[k]:3s}) {k:6s} median {med[k]:8.4f}  min {min(ms[k]):8.4f}  "
@@ -190,6 +197,16 @@ def measure(name, shape, runs, epochs, track_hard=False):
               f"{hh['hard_objective'][2:].min():.6g} .. {hh['hard_objective'][2:].max():.6g}, "
               f"over-time fibers {hh['hard_overtime'][2:].min()} .. {hh['hard_overtime'][2:].max()}, "
               f"best hard epoch {hb['epoch']} utility {hb['utility']:.6g}")
+    if track_hard == "budget":
+        bl = variants[5][1].loop
+        bh, bb = bl.history(), bl.hard_best()
+        assert np.isfinite(bh["hard_objective"]).all(), "the budget hard_objective is not finite"
+        print(f"  (c+b) - (c) = {1e3 * (med['loop+b'] - med['loop']):8.2f} us per epoch; (c+b) - (c+h) "
+              f"= {1e3 * (med['loop+b'] - med['loop+h']):.2f} us; run-to-run spread of (c+b) "
+              f"{1e3 * (max(ms['loop+b']) - min(ms['loop+b'])):.2f} us; budget hard objective "
+              f"{bh['hard_objective'][2:].min():.6g} .. {bh['hard_objective'][2:].max():.6g}, "
+              f"over-time fibers {bh['hard_overtime'][2:].min()} .. {bh['hard_overtime'][2:].max()}, "
+              f"best hard epoch {bb['epoch']} utility {bb['utility']:.6g}")
     hist = variants[2][1].loop
     b = hist.best()
     h = hist.history()
@@ -209,8 +226,10 @@ def main():
     ap.add_argument("--shape", default="both", choices=["ref", "bench", "both"])
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--epochs", type=int, default=200)
-    ap.add_argument("--track-hard", action="store_true",
-                    help="add (c+h): TrainLoop(track_hard=True), and report (c+h) - (c)")
+    ap.add_argument("--track-hard", nargs="?", const="floor", default=False,
+                    choices=["floor", "budget"],
+                    help="add (c+h): TrainLoop(track_hard=True), and report (c+h) - (c); "
+                         "'budget' also adds (c+b): track_hard='budget'")
     a = ap.parse_args()
     print(f"device {torch.cuda.get_device_name(0)}; torch {torch.__version__}")
     for name in (["ref", "bench"] if a.shape == "both" else [a.shape]):
