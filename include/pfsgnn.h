@@ -297,9 +297,12 @@ int pfsgnn_target_global_fwd(
  * NF bt2, tmask), then ONE launch for the class side -- the per-class sums of
  * the edge kernel's partials, node_mlp_2 + BatchNorm1d, the GlobalModel and the
  * next block's Pt / Qt -- with every output of pfsgnn_target_global_fwd.  The
- * class launch runs G * ceil(NC / 32) units of 32 classes on at most one
- * workgroup per CU with one device-wide barrier between node_mlp_2 (and its
- * BatchNorm partials) and the norm.  The grid must be co-resident (checked
+ * class launch runs G * ceil(NC / CT) units of CT classes of one graph, CT the
+ * smaller of 16 and 32 that keeps G * ceil(NC / CT) <= 512 units and at most
+ * 64 per graph (so NC <= 2048; a batch past that is refused before anything
+ * is launched), on at most one workgroup per CU -- a workgroup walks units
+ * blockIdx, blockIdx + grid, ... -- with one device-wide barrier between
+ * node_mlp_2 (and its BatchNorm partials) and the norm.  The grid must be co-resident (checked
  * against the occupancy API: an error otherwise); a barrier wait that outlives
  * ~1.5 s -- a workgroup never scheduled because another process holds the
  * CUs -- raises pfsgnn_sync_faults' count and traps, so the launch fails
@@ -343,7 +346,10 @@ size_t pfsgnn_block_tail_bytes(void);
  *      [F, 3F) written to g_agg, [3F, 4F) to gu_t; and g_hsum = Wt2^T g_agg
  *      (TModel's second Linear, gnn.py:188-190).
  * node_mlp_2: W1 [4F][4F], W2 [F][4F]; GlobalModel: gW1 [gH][3F], gW2 [F][gH],
- * RMSNorm weight w (NULL: unnormed, then y1/r1/r2/dwp unused).  Replaces
+ * RMSNorm weight w (NULL: unnormed, then y1/r1/r2/dwp unused).  nunits =
+ * G * ceil(NC / 16) units: at most 64 per graph (NC <= 1024) and 4096 in all,
+ * walked by min(nunits, CUs) workgroups; ws >= nunits * (F + 32) floats (the
+ * units' u-gradient partials and BatchNorm sums).  Replaces
  * graph_reduce_multi + global_bwd (2 launches) + mlp_bwd (2) + lin_t. */
 typedef struct {
   int G, NF, NC, F;

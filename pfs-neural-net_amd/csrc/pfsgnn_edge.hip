@@ -1815,6 +1815,7 @@ extern "C" size_t pfsgnn_sl_tmask_bytes(const pfsgnn_sliced_t* sl, int F) {
 }
 
 namespace pf {
+bool tail_units_ok(int G, int NC);
 int class_tail_fwd(const pfsgnn_block_tail& a, const float* cpart, int BPG, float bscale,
                    float* scratch, hipStream_t st);
 }
@@ -1887,6 +1888,8 @@ extern "C" int pfsgnn_target_block_fwd(const pfsgnn_block_tail* a, void* ws, siz
   PF_REQUIRE(!a->We || (a->be && a->Ws && a->bs && a->Pt && a->Qt), where,
              "next-block parts need be, Ws, bs, Pt, Qt");
   PF_REQUIRE((long long)G * NC > 1, where, "BatchNorm needs more than one class");
+  PF_REQUIRE(pf::tail_units_ok(G, NC), where,
+             "more than 512 class units (G * ceil(NC / 32)) or NC > 2048");
   const EdgeGeo geo = geo_of(G, NF, NC, nullptr);
   Ws w{reinterpret_cast<char*>(ws), ws_bytes};
   float* part = w.take((size_t)G * col_bpg(geo, nullptr) * NC * 2 * F);

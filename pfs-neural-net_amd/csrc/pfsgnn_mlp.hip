@@ -829,7 +829,7 @@ __global__ __launch_bounds__(CG_THREADS) void k_class_global_fwd(ClassGlobalArgs
 
 // ---------------------------------------------------------------- fused block tail
 // A block's whole class side on a complete batch in ONE launch
-// (pfsgnn_target_block_fwd): units of 32 classes of one graph, one workgroup
+// (pfsgnn_target_block_fwd): units of 16 or 32 classes of one graph (tail_ct), one workgroup
 // per CU at most (persistent over the units), in two phases around one
 // device-wide barrier:
 //   1. TModel's per-class sum of the edge kernel's column partials (hsum, its
@@ -2152,6 +2152,9 @@ static int tail_ct(int G, int NC) {
   }
   return 0;
 }
+// whether the class launch takes the batch: pfsgnn_target_block_fwd asks before
+// its edge launch, so a refused call launches nothing
+bool tail_units_ok(int G, int NC) { return tail_ct(G, NC) > 0; }
 size_t tail_ws_floats(int G, int NC, int F) {
   const int ct = tail_ct(G, NC);
   const size_t nu = (size_t)G * ((NC + (ct ? ct : CT_CLS) - 1) / (ct ? ct : CT_CLS));
