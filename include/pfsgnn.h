@@ -120,13 +120,18 @@ int pfsgnn_timing_query(const char* name, double* total_ms, long long* count);
  * MLP (gnn.py:65), SModel.node_mlp_2 (gnn.py:154), TModel.node_mlp_2
  * (gnn.py:192), GlobalModel (gnn.py:223) and the encoders (gnn.py:297).   */
 
-/* Y[m][n] (+)= sum_k W[m][k] * act(X[k][n]) + bscale*b[m]; act = lrelu if act_in */
+/* Y[m][n] (+)= sum_k W[m][k] * act(X[k][n]) + bscale*b[m]; act = lrelu if act_in.
+ * pfsgnn_lin, _lin_cat and _lin_gather take K <= 160 input and M <= 176 output
+ * rows, pfsgnn_lin_t M <= 160 and K <= 176 (its input and output widths);
+ * wider shapes are refused before any launch. */
 int pfsgnn_lin(const float* W, int ldw, int M, int K, const float* X, int N,
                const float* b, float bscale, int act_in, float* Y, int add, void* stream);
 /* pfsgnn_lin + per-column gathers in the epilogue:
  * Y[m][n] (+)= (W . act(X))[m][n] + bscale*b[m] + G1[m][idx1[n]] + G2[m][idx2[n]]
- * (G1/G2 [M][ld] node tables or NULL) -- the general-graph path's first
- * per-edge Linear, gnn.py:100/136/188, with its node parts gathered per edge */
+ * (G1/G2 [M][ld] node tables or NULL, idx in [0, ld)) -- the general-graph
+ * path's first per-edge Linear, gnn.py:100/136/188, with its node parts
+ * gathered per edge.  With a gather M, K <= 64 (refused otherwise); without
+ * one it is pfsgnn_lin, limits included. */
 int pfsgnn_lin_gather(const float* W, int ldw, int M, int K, const float* X, int N,
                       const float* b, float bscale, int act_in, float* Y, int add,
                       const float* G1, const int* idx1, int ld1, const float* G2, const int* idx2,
@@ -169,9 +174,18 @@ int pfsgnn_wgrad_cat(const float* dY, int M, const pfsgnn_seg* segs, int nseg, i
  * optimizer step, so their cross-block reductions can run together, after the
  * backward: pfsgnn_wgrad_cat_part launches the per-block partials into `part`
  * (pfsgnn_wgrad_part_bytes(M, K, N, has_db) bytes, owned by the caller until
- * the reduction has run) and returns up to 5 reduction descriptors in red_out;
+ * the reduction has run) and returns up to 5 reduction descriptors in red_out
+ * (one per input block, then one for db);
  * pfsgnn_reduce_batch finishes any list of them in as few launches as the
- * descriptors' output overlaps allow (fixed order: deterministic).          */
+ * descriptors' output overlaps allow (fixed order: deterministic; two
+ * reductions into the same cells never share a launch, so a later one sees
+ * the earlier one's result).
+ * A descriptor: out[r][c] (+)= scale * sum_b part[b*plen + r*ldp + c], r <
+ * rows <= 65535, c < cols <= 32767 (wider ones are refused, nothing launched).
+ * `part` is NOT read-only: a reduction of more than 512 partials first sums
+ * every segment of 256 partials into the segment's first row IN PLACE, so the
+ * caller's buffer no longer holds the partials afterwards, and two
+ * descriptors of one call must not share such a buffer. */
 typedef struct {
   const float* part;
   int nb;

@@ -712,38 +712,47 @@ extern "C" int pfsgnn_gemm_multi(const pfsgnn_gemm_job* jobs, int n, void* strea
 #undef PF_GMA
     attr = true;
   }
+  // every job is checked and its table entry formed before the first launch:
+  // a refused batch writes nothing
+  std::vector<GemmJob> JJ(n);
+  for (int i = 0; i < n; ++i) {
+    const pfsgnn_gemm_job& jb = jobs[i];
+    PF_REQUIRE(jb.W && jb.Y && jb.M > 0 && jb.N > 0 && (jb.trans == 0 || jb.trans == 1), where,
+               "bad job");
+    GemmJob& J = JJ[i];
+    int Ki;
+    if (jb.trans) {
+      PF_REQUIRE(jb.nseg == 1 && jb.segs && jb.segs[0].x && !jb.segs[0].per_graph, where,
+                 "lin_t job takes one plain input block");
+      J.S = one_seg(jb.segs[0].x, 0);
+      Ki = jb.K;
+    } else {
+      Ki = make_segs(jb.segs, jb.nseg, jb.N, J.S);
+      PF_REQUIRE(Ki > 0, where, "bad segment list");
+    }
+    PF_REQUIRE(Ki <= 40 && jb.M <= 64, where, "job wider than the batched kernels (K 40, M 64)");
+    J.W = jb.W;
+    J.b = jb.b;
+    J.Z = jb.Z;
+    J.Y = jb.Y;
+    J.ldw = jb.ldw;
+    J.trans = jb.trans;
+    J.Mo = jb.M;
+    J.Ki = Ki;
+    J.N = jb.N;
+    J.act_in = jb.act_in;
+    J.add = jb.add;
+    J.bscale = jb.bscale;
+  }
   for (int i0 = 0; i0 < n; i0 += GM_MULTI) {
     const int m = std::min(GM_MULTI, n - i0);
     GemmTable T{};
     int blocks = 0, mt = 1, ks = 3;
     for (int u = 0; u < m; ++u) {
       const pfsgnn_gemm_job& jb = jobs[i0 + u];
-      PF_REQUIRE(jb.W && jb.Y && jb.M > 0 && jb.N > 0 && (jb.trans == 0 || jb.trans == 1), where,
-                 "bad job");
       GemmJob& J = T.j[u];
-      int Ki;
-      if (jb.trans) {
-        PF_REQUIRE(jb.nseg == 1 && jb.segs && jb.segs[0].x && !jb.segs[0].per_graph, where,
-                   "lin_t job takes one plain input block");
-        J.S = one_seg(jb.segs[0].x, 0);
-        Ki = jb.K;
-      } else {
-        Ki = make_segs(jb.segs, jb.nseg, jb.N, J.S);
-        PF_REQUIRE(Ki > 0, where, "bad segment list");
-      }
-      PF_REQUIRE(Ki <= 40 && jb.M <= 64, where, "job wider than the batched kernels (K 40, M 64)");
-      J.W = jb.W;
-      J.b = jb.b;
-      J.Z = jb.Z;
-      J.Y = jb.Y;
-      J.ldw = jb.ldw;
-      J.trans = jb.trans;
-      J.Mo = jb.M;
-      J.Ki = Ki;
-      J.N = jb.N;
-      J.act_in = jb.act_in;
-      J.add = jb.add;
-      J.bscale = jb.bscale;
+      J = JJ[i0 + u];
+      const int Ki = J.Ki;
       J.blk0 = blocks;
       blocks += (jb.N + 63) / 64;
       mt = std::max(mt, (jb.M + 15) / 16);
@@ -752,15 +761,12 @@ extern "C" int pfsgnn_gemm_multi(const pfsgnn_gemm_job* jobs, int n, void* strea
     }
     T.njob = m;
     const size_t lds = (size_t)mt * 16 * (4 * ks + 1) * sizeof(float);
-    bool launched = false;
+    // (M <= 64 and K <= 40 give mt in 1..4 and ks in {3, 5, 10}: every pair is in PF_GMM_ALL)
 #define PF_GMM(TT, KK)                                                                       \
-  if (!launched && mt == TT && ks == KK) {                                                   \
-    hipLaunchKernelGGL((k_gemm_multi<TT, KK>), dim3(blocks), dim3(256), lds, st, T);         \
-    launched = true;                                                                         \
-  }
+  if (mt == TT && ks == KK)                                                                  \
+    hipLaunchKernelGGL((k_gemm_multi<TT, KK>), dim3(blocks), dim3(256), lds, st, T);
     PF_GMM_ALL(PF_GMM)
 #undef PF_GMM
-    PF_REQUIRE(launched, where, "no kernel for this shape");
   }
   return pf::check_launch(where);
 }
@@ -1123,9 +1129,23 @@ static bool wg_allow_lds(Fn fn) {
                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;
 }
 
+// (tm, per) pairs instantiated.  wgrad_plan reaches 14 of them over M, K <= 256:
+// (1,1) (1,2) (1,4) (1,8) (2,4) (2,8) (2,16) (4,4) (4,8) (4,16) (8,8) (8,16)
+// (16,8) (16,16); per 16 with tm < 16 is a short, wide product (M + K + 1 >
+// 256 in at most 64 tiles, e.g. 10 x 250).  (2,1) (2,2) (4,1) (4,2) (8,1)
+// (8,2) (8,4) (16,1) (16,2) (16,4) are instantiated but never selected (tm
+// tiles per wave need more staged rows than per allows);
+// tests/test_node_linalg_ref.py enumerates both lists.
+// (2,16) (4,16) (8,16): no scratch and no VGPR spill in either form (207 /
+// 221 / 249 VGPRs bf16x3, 166 / 172 / 200 fp32; the kernel-resource-usage
+// remarks of `make resource-usage`).  (4,16) and (8,16) take the bf16x3 form
+// by wg_x3_for's tm >= 4 rule like their per <= 8 neighbours; whether it is
+// the faster form at per 16 has not been measured (no model layer has such a
+// shape: K <= 160 in the GEMMs leaves them to direct callers).
 #define PF_WG_ALL(X) \
-  X(1, 1) X(1, 2) X(1, 4) X(1, 8) X(2, 1) X(2, 2) X(2, 4) X(2, 8) X(4, 1) X(4, 2) X(4, 4) \
-  X(4, 8) X(8, 1) X(8, 2) X(8, 4) X(8, 8) X(16, 1) X(16, 2) X(16, 4) X(16, 8) X(16, 16)
+  X(1, 1) X(1, 2) X(1, 4) X(1, 8) X(2, 1) X(2, 2) X(2, 4) X(2, 8) X(2, 16) X(4, 1) X(4, 2) \
+  X(4, 4) X(4, 8) X(4, 16) X(8, 1) X(8, 2) X(8, 4) X(8, 8) X(8, 16) X(16, 1) X(16, 2)     \
+  X(16, 4) X(16, 8) X(16, 16)
 
 // Launches the per-block partials of dW (and db) into ws and describes the
 // reduction that finishes them (rd[0..*nr)); the caller launches it now or
@@ -1459,10 +1479,15 @@ static bool red_overlap(const RedDesc& a, const RedDesc& b) {
 }
 
 static int reduce_batch_desc(const std::vector<RedDesc>& reds, hipStream_t st) {
-  std::vector<RedDesc> group;
+  // every descriptor is checked before the first launch (overlapping outputs
+  // split a list into several): a refused list writes nothing
   for (const RedDesc& d : reds) {
     PF_REQUIRE(d.part && d.out && d.nb > 0 && d.rows > 0 && d.cols > 0, "pfsgnn_reduce_batch",
                "bad reduction");
+    PF_REQUIRE(red_fits(d), "pfsgnn_reduce_batch", "reduction wider than the packed descriptor");
+  }
+  std::vector<RedDesc> group;
+  for (const RedDesc& d : reds) {
     bool clash = (int)group.size() == PF_MAX_RED;
     for (const RedDesc& g : group) clash = clash || red_overlap(g, d);
     if (clash) {  // a launch never holds two reductions into the same cells
