@@ -1069,6 +1069,97 @@ size_t pfsgnn_schedule_budget_ws_bytes(int G, int NF, int NC, long long EP);
 int pfsgnn_schedule_budget(const pfsgnn_schedule_budget_args* a, void* ws, size_t ws_bytes,
                            void* stream);
 
+/* ---------------------------------------------------------------- observing plan
+ * pfsgnn_schedule_plan -- from an integer schedule to the plan an observer
+ * runs: visits capped by the galaxies a class has per field (train.py:41's
+ * N_i = class_info[:, 1] / NFIELDS, which train.py:57-58 only penalises),
+ * each fiber's classes laid end to end (train.py:256-261: cumulative =
+ * np.cumsum(rounded, axis=1), left = hstack(0, cumulative[:, :-1])) and every
+ * single exposure listed at left + m * class_req (train.py:283-284).  The op
+ * never reads the edge state: its input is visits_in [E] int32 in the caller's
+ * edge order (pfsgnn_schedule's or pfsgnn_schedule_budget's visits, or any
+ * other).  Edges are indexed by edge_index; repeated pairs are separate edges,
+ * told apart by their caller position.  T = ci row 0, N = ci row 1.
+ *  1. Sanitise.  T_e = T[tgt_e]; an edge whose T_e is not finite or <= 0 is
+ *     INERT, w_e = 0 (pfsgnn_schedule_budget's rule); else w_e =
+ *     min(max(visits_in_e, 0), 2^24).
+ *  2. Class cap, only with cap = 1.  q_c = N_c / nfields (one IEEE fp32
+ *     division, the first quotient of completeness); cap_c = floorf(q_c) as an
+ *     integer, 0 for a NaN or negative q_c, no cap for q_c >= 2^31.  S_c = sum
+ *     of w_e over tgt_e = c (int64).  A class with S_c <= cap_c is untouched.
+ *     Else the max-min fair trim: L the largest integer >= 0 with sum_e
+ *     min(w_e, L) <= cap_c, rem = cap_c - sum_e min(w_e, L); edges with w_e <= L
+ *     keep w_e; of the edges with w_e > L, taken in ascending (src_e, caller
+ *     position) order, the first rem get L + 1 and the rest L.  cut_c = S_c -
+ *     cap_c for a trimmed class, else 0 (int64).  Trimming only removes visits.
+ *  3. Timeline.  A fiber's plan order is ascending (tgt_e, caller position).
+ *     dur_e = (double)visits_e * (double)T_e (exact; 0 for 0 visits); start_e
+ *     the double sum of dur over the fiber's earlier edges, stored as fp32
+ *     (rounded once); used_f the fiber's total as fp32; idle_f = (double)
+ *     total_time - total as fp32 (negative for a fiber that is over); cnt_f =
+ *     sum of visits_e (int64).
+ *  4. Target list.  seg_ptr [G*NF + 1] int64: the exclusive scan of cnt, always
+ *     complete (seg_ptr[G*NF] is the size to allocate).  Visit m of edge e has
+ *     index i = seg_ptr[src_e] + (visits of the fiber's earlier edges in plan
+ *     order) + m; seg_edge[i] = e (caller position, int32), seg_start[i] =
+ *     fp32(start_e + m * T_e) evaluated in double on the unrounded start_e.
+ *     Only i < seg_cap is written; seg_edge and seg_start may be NULL with
+ *     seg_cap = 0 (a count-only call).
+ *  5. Aggregates on the final visits, by pfsgnn_schedule's formulas: n_hard
+ *     [G*NC] int32 (the low 32 bits of the int64 class sum: exact below 2^31,
+ *     which a capped class always is), completeness [G*NC], utility [G],
+ *     over [G] (fibers whose double total exceeds total_time), worst [G] (the
+ *     largest used_f).
+ * Batch, one of two forms.  Complete: mode 0..2 and perm as pfsgnn_schedule
+ * takes them, every CSR pointer NULL, E ignored.  General: mode = -1, perm
+ * NULL, E and the six arrays of pfsgnn_sparse_layout (not the sliced layout:
+ * the op runs on every general batch, those of the composed path included).
+ * Exactness contract.  When T lies on the 2^-20 grid below 2^20 every double
+ * sum is exact and the result is a pure function of (visits_in, edge_index,
+ * ci, total_time, nfields): identical for every caller order and both batch
+ * forms.  Otherwise the op is bitwise reproducible run to run, the integer
+ * outputs (visits, cut, n_hard, seg_ptr, seg_edge) are still exact and the
+ * fp32 times are within one fp32 ulp of the sequential double sum (a complete
+ * batch sums a fiber's classes in order; a general batch sums them by a fixed
+ * tree of 64-edge chunks).
+ * Workspace: pfsgnn_schedule_plan_ws_bytes(G, NF, NC, E) (E = 0: complete) --
+ * complete: one word per edge and the fiber tables; general: three words per
+ * edge (the plan-order sort's keys, ping and pong, and the plan order; the
+ * sanitised visits reuse the key buffer), the sort's temporary and the fiber
+ * tables.  Nothing allocates, synchronises or uses float atomics: capturable.
+ * Refused before any launch: a null struct; both batch forms, or neither; mode
+ * outside 0..2; mode 0 without perm; a CSR form with a null array; a null
+ * required output or input; seg_cap > 0 with a null segment array; seg_cap <
+ * 0; cap outside {0, 1}; non-positive dims; E >= 2^31; a workspace too
+ * small. */
+typedef struct pfsgnn_schedule_plan_args {
+  int G, NF, NC;
+  int mode;                  /* complete: 0 perm, 1 fiber-major, 2 canonical; general: -1 */
+  const int32_t* perm;
+  long long E;               /* general: the edges; complete: ignored */
+  const int *src_p, *tgt_p, *user_of, *fib_ptr, *cls_ord, *cls_ptr;
+  const float* ci;
+  float total_time, nfields;
+  const int32_t* visits_in;
+  int cap;
+  long long seg_cap;
+  int32_t* visits;           /* [E], caller's order */
+  float *start;              /* [E], caller's order */
+  float *used, *idle;        /* [G*NF] */
+  int32_t* n_hard;           /* [G*NC] */
+  float *completeness, *utility;
+  int32_t* over;
+  float* worst;
+  long long* cut;            /* [G*NC] */
+  long long* seg_ptr;        /* [G*NF + 1] */
+  int32_t* seg_edge;         /* [seg_cap] or NULL */
+  float* seg_start;          /* [seg_cap] or NULL */
+} pfsgnn_schedule_plan_args;
+size_t pfsgnn_schedule_plan_args_bytes(void);
+size_t pfsgnn_schedule_plan_ws_bytes(int G, int NF, int NC, long long E);
+int pfsgnn_schedule_plan(const pfsgnn_schedule_plan_args* a, void* ws, size_t ws_bytes,
+                         void* stream);
+
 /* ---------------------------------------------------------------- training loop
  * The per-epoch bookkeeping of train.py:133-165 as three small launches, so a
  * whole epoch (these, the forward, the loss, the backward, pfsgnn_adam) is one

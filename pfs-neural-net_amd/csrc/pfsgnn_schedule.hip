@@ -23,6 +23,9 @@
 #include "pfsgnn_mfma.h"
 #include "../../include/pfsgnn.h"
 
+#include <hipcub/hipcub.hpp>
+
+#include <algorithm>
 #include <cmath>
 
 namespace {
@@ -776,5 +779,436 @@ extern "C" int pfsgnn_schedule_budget(const pfsgnn_schedule_budget_args* a, void
   hipLaunchKernelGGL(k_schedule_finish, dim3(G), dim3(256), 0, st, NF, NC, G * NC, NFG, 1,
                      (long long)G * NF, part, a->fiber_time, a->ci, a->total_time, a->nfields,
                      a->n_hard, a->fiber_time, a->completeness, a->utility, a->over, a->worst);
+  return pf::check_launch(where);
+}
+
+// ================================================================ observing plan
+namespace {
+// pfsgnn_schedule_plan (include/pfsgnn.h): class-capped visits, fiber timelines
+// and the target list.  The edge state is never read; the op's working set is
+// one int32 word per edge (the sanitised, then trimmed, visit count) in
+// canonical order (complete: a class's NF words contiguous) or in CSR position
+// order (general: a class's words gathered through cls_ord, a fiber's through
+// the plan order below).  Launches:
+//   general only: k_plan_keys + one stable radix sort of cls_ord -- (tgt, src,
+//      position) order -- by src: the plan order (src, tgt, position), whose
+//      fiber runs are fib_ptr's;
+//   1. k_plan_class, a block per class: gather + sanitise (the one read of
+//      visits_in), the int64 class sum, and for a class over its cap the level
+//      L by bisection (int64 block sums over the class's words: in LDS up to
+//      PLAN_LDS of them, else re-read by the thread that wrote them) and the
+//      ranks of the edges above the level by ballot scans in edge order;
+//   2. k_plan_fiber<false> (complete: a lane per fiber walking its classes with
+//      a double running sum) / k_plan_fiber_csr<false> (general: a wave per
+//      fiber, 64 edges of its plan-order run per step, wave scans of the double
+//      durations and the int64 counts -- a hub's degree has no bound): visits,
+//      start, used, idle, the fiber's count and its over flag;
+//   3. k_plan_finish, a block per graph; one device scan of the counts;
+//   4. the same fiber kernels with FILL: the walk again, writing the segments.
+constexpr int PLAN_LDS = 8192;
+constexpr int PLAN_WMAX = 1 << 24;
+
+// sum / max over the block of 256 in every thread (red: 4 words of LDS)
+__device__ __forceinline__ long long plan_block_sum(long long v, long long* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (red[0] + red[1]) + (red[2] + red[3]);
+}
+__device__ __forceinline__ int plan_block_max(int v, long long* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (int)max(max(red[0], red[1]), max(red[2], red[3]));
+}
+
+__global__ __launch_bounds__(256) void k_plan_keys(long long E, const int* __restrict__ src_p,
+                                                   const int* __restrict__ cls_ord,
+                                                   int* __restrict__ key) {
+  for (long long k = (long long)blockIdx.x * 256 + threadIdx.x; k < E;
+       k += (long long)gridDim.x * 256)
+    key[k] = src_p[cls_ord[k]];
+}
+
+template <bool CSR>
+__global__ __launch_bounds__(256) void k_plan_class(
+    int NF, int NC, int NT, int mode, const int32_t* __restrict__ perm,
+    const int* __restrict__ cls_ord, const int* __restrict__ cls_ptr,
+    const int* __restrict__ user_of, const float* __restrict__ ci, float nfields, int cap,
+    const int32_t* __restrict__ visits_in, int* w, int32_t* __restrict__ n_hard,
+    float* __restrict__ completeness, long long* __restrict__ cut) {
+  __shared__ int lw[PLAN_LDS];
+  __shared__ long long red[4];
+  __shared__ int wtot[4];
+  const int cn = blockIdx.x, t = threadIdx.x;
+  const int gg = cn / NC, c = cn - gg * NC;
+  const float T = ci[cn];
+  const bool inert = !(T > 0.f) || !(T < INFINITY);
+  long long k0;
+  int n;
+  if (CSR) {
+    k0 = cls_ptr[cn];
+    n = cls_ptr[cn + 1] - (int)k0;
+  } else {
+    k0 = ((long long)gg * NC + c) * NF;
+    n = NF;
+  }
+  // edge k of the class, in ascending (src, caller position) order: its word
+  auto slot = [&](int k) -> long long { return CSR ? (long long)cls_ord[k0 + k] : k0 + k; };
+  const bool inl = n <= PLAN_LDS;
+  auto get = [&](int k) -> int { return inl ? lw[k] : w[slot(k)]; };
+  // (a thread only ever re-reads the words it wrote: k = t mod 256 throughout)
+  long long S = 0;
+  int mx = 0;
+  for (int k = t; k < n; k += 256) {
+    const long long s = slot(k);
+    long long u;
+    if (CSR) u = user_of[s];
+    else u = mode == 2 ? s : (mode == 1 ? ((long long)gg * NF + k) * NC + c : (long long)perm[s]);
+    int v = visits_in[u];
+    v = inert ? 0 : min(max(v, 0), PLAN_WMAX);
+    w[s] = v;
+    if (inl) lw[k] = v;
+    S += v;
+    mx = max(mx, v);
+  }
+  S = plan_block_sum(S, red);
+  const float Ni = ci[NT + cn] / nfields;      // one IEEE division
+  long long capc = 0;
+  bool capped = cap != 0;
+  if (Ni != Ni || Ni < 0.f) capc = 0;
+  else if (Ni >= 2147483648.f) capped = false;
+  else capc = (long long)floorf(Ni);
+  long long nfin = S, cutc = 0;
+  if (capped && S > capc) {                    // (block-uniform)
+    mx = plan_block_max(mx, red);
+    // f(L) = sum min(w, L): f(0) = 0 <= cap, f(mx) = S > cap
+    int lo = 0, hi = mx;
+    long long flo = 0;
+    while (hi - lo > 1) {
+      const int mid = lo + (hi - lo) / 2;
+      long long s = 0;
+      for (int k = t; k < n; k += 256) s += min(get(k), mid);
+      s = plan_block_sum(s, red);
+      if (s <= capc) {
+        lo = mid;
+        flo = s;
+      } else {
+        hi = mid;
+      }
+    }
+    const int L = lo;
+    const long long rem = capc - flo;
+    // the edges above the level, ranked in edge order: the first rem keep L + 1
+    const int lane = t & 63, wv = t >> 6;
+    long long carry = 0;
+    for (int kb = 0; kb < n; kb += 256) {
+      const int k = kb + t;
+      const bool above = k < n && get(k) > L;
+      const unsigned long long b = __ballot(above);
+      const int inw = __popcll(b & ((1ull << lane) - 1ull));
+      __syncthreads();
+      if (lane == 0) wtot[wv] = __popcll(b);
+      __syncthreads();
+      long long rank = carry + inw;
+      for (int j = 0; j < wv; ++j) rank += wtot[j];
+      if (above) w[slot(k)] = L + (rank < rem ? 1 : 0);
+      carry += (wtot[0] + wtot[1]) + (wtot[2] + wtot[3]);
+    }
+    nfin = capc;
+    cutc = S - capc;
+  }
+  if (t == 0) {
+    n_hard[cn] = (int32_t)nfin;
+    completeness[cn] = (float)(int32_t)nfin / Ni;
+    cut[cn] = cutc;
+  }
+}
+
+struct PlanOut {
+  int32_t* visits;
+  float *start, *used, *idle;
+  long long* cnt;
+  int* ovf;
+  const long long* seg_ptr;
+  long long seg_cap;
+  int32_t* seg_edge;
+  float* seg_start;
+};
+
+// visit m of an edge with v visits: at i0 + m, start + m T in double
+__device__ __forceinline__ void plan_fill(const PlanOut& o, long long i0, int v, int u, double st,
+                                          double Td) {
+  for (int m = 0; m < v; ++m) {
+    const long long i = i0 + m;
+    if (i >= o.seg_cap) break;
+    o.seg_edge[i] = u;
+    o.seg_start[i] = (float)(st + (double)m * Td);   // (m T exact: 24 x 24 bits)
+  }
+}
+
+template <bool FILL>
+__global__ __launch_bounds__(256) void k_plan_fiber(int NF, int NC, int NFB, long long NS, int mode,
+                                                    const int32_t* __restrict__ perm,
+                                                    const int* __restrict__ w,
+                                                    const float* __restrict__ ci, float total_time,
+                                                    PlanOut o) {
+  const int gg = blockIdx.x / NFB, f = (blockIdx.x - gg * NFB) * 256 + threadIdx.x;
+  if (f >= NF) return;
+  const long long n = (long long)gg * NF + f;
+  const long long e0 = (long long)gg * NC * NF + f;
+  const float* Tg = ci + (long long)gg * NC;
+  double run = 0.0;
+  long long c = 0;
+  const long long i0 = FILL ? o.seg_ptr[n] : 0;
+#pragma unroll 4
+  for (int k = 0; k < NC; ++k) {
+    const long long e = e0 + (long long)k * NF;   // canonical: consecutive fibers, coalesced
+    const int v = w[e];
+    const long long u = mode == 2 ? e : (mode == 1 ? n * NC + k : (long long)perm[e]);
+    const double Td = (double)Tg[k];
+    if (FILL) {
+      plan_fill(o, i0 + c, v, (int)u, run, Td);
+    } else {
+      o.visits[u] = v;
+      o.start[u] = (float)run;
+    }
+    if (v) run += (double)v * Td;                 // (exact product; an inert T never enters)
+    c += v;
+  }
+  if (!FILL) {
+    o.used[n] = (float)run;
+    o.idle[n] = (float)((double)total_time - run);
+    o.cnt[n] = c;
+    o.ovf[n] = run > (double)total_time ? 1 : 0;
+    if (n == 0) o.cnt[NS] = 0;
+  }
+}
+
+template <bool FILL>
+__global__ __launch_bounds__(256) void k_plan_fiber_csr(
+    long long NS, const int* __restrict__ fib_ptr, const int* __restrict__ pord,
+    const int* __restrict__ tgt_p, const int* __restrict__ user_of, const int* __restrict__ w,
+    const float* __restrict__ ci, float total_time, PlanOut o) {
+  const int lane = threadIdx.x & 63;
+  const long long n = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (n >= NS) return;                            // the whole wave
+  const int p0 = fib_ptr[n], p1 = fib_ptr[n + 1];
+  double run = 0.0;
+  long long c = 0;
+  const long long i0 = FILL ? o.seg_ptr[n] : 0;
+  for (int kb = p0; kb < p1; kb += 64) {
+    const int k = kb + lane;
+    const bool in = k < p1;
+    const int p = in ? pord[k] : 0;
+    const int v = in ? w[p] : 0;
+    const int u = in ? user_of[p] : 0;
+    const double Td = in ? (double)ci[tgt_p[p]] : 0.0;
+    // inclusive wave scans of the duration and the count, in plan order
+    double ds = v ? (double)v * Td : 0.0;
+    long long cs = v;
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) {
+      const double d2 = __shfl_up(ds, s);
+      const long long c2 = __shfl_up(cs, s);
+      if (lane >= s) {
+        ds += d2;
+        cs += c2;
+      }
+    }
+    double de = __shfl_up(ds, 1);
+    long long ce = __shfl_up(cs, 1);
+    if (lane == 0) {
+      de = 0.0;
+      ce = 0;
+    }
+    const double st = run + de;
+    if (in) {
+      if (FILL) {
+        plan_fill(o, i0 + c + ce, v, u, st, Td);
+      } else {
+        o.visits[u] = v;
+        o.start[u] = (float)st;
+      }
+    }
+    run += __shfl(ds, 63);
+    c += __shfl(cs, 63);
+  }
+  if (!FILL && lane == 0) {
+    o.used[n] = (float)run;
+    o.idle[n] = (float)((double)total_time - run);
+    o.cnt[n] = c;
+    o.ovf[n] = run > (double)total_time ? 1 : 0;
+    if (n == 0) o.cnt[NS] = 0;
+  }
+}
+
+// a block per graph: utility = min completeness, the fibers over, the largest used
+__global__ __launch_bounds__(256) void k_plan_finish(int NF, int NC,
+                                                     const float* __restrict__ completeness,
+                                                     const float* __restrict__ used,
+                                                     const int* __restrict__ ovf,
+                                                     float* __restrict__ utility,
+                                                     int* __restrict__ over,
+                                                     float* __restrict__ worst) {
+  const int g = blockIdx.x, t = threadIdx.x;
+  __shared__ float smin[256], smax[256];
+  __shared__ int sover[256];
+  float mn = INFINITY, mx = 0.f;
+  int ov = 0;
+  for (int c = t; c < NC; c += 256) mn = nan_min(mn, completeness[(long long)g * NC + c]);
+  for (int f = t; f < NF; f += 256) {
+    const long long n = (long long)g * NF + f;
+    mx = nan_max(mx, used[n]);
+    ov += ovf[n];
+  }
+  smin[t] = mn;
+  smax[t] = mx;
+  sover[t] = ov;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (t < s) {
+      smin[t] = nan_min(smin[t], smin[t + s]);
+      smax[t] = nan_max(smax[t], smax[t + s]);
+      sover[t] += sover[t + s];
+    }
+    __syncthreads();
+  }
+  if (t == 0) {
+    utility[g] = smin[0];
+    over[g] = sover[0];
+    worst[g] = smax[0];
+  }
+}
+
+int plan_key_bits(long long n) {  // keys are 0..n-1
+  int b = 1;
+  while (b < 31 && (1ll << b) < n) ++b;
+  return b;
+}
+
+struct PlanWs {
+  size_t words, cnt, ovf, tmp, total;
+};
+PlanWs plan_ws(int G, int NF, int NC, long long E) {
+  const long long NS = (long long)G * NF;
+  const bool csr = E > 0;
+  const long long edges = csr ? E : NS * NC;
+  size_t tscan = 0, tsort = 0;
+  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, tscan, (const long long*)nullptr,
+                                         (long long*)nullptr, (int)(NS + 1));
+  if (csr)
+    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, tsort, (const int*)nullptr, (int*)nullptr,
+                                             (const int*)nullptr, (int*)nullptr, (int)edges);
+  PlanWs p;
+  p.words = align256((size_t)edges * sizeof(int));
+  p.cnt = align256((size_t)(NS + 1) * sizeof(long long));
+  p.ovf = align256((size_t)NS * sizeof(int));
+  p.tmp = align256(std::max(tscan, tsort)) + 256;
+  p.total = (csr ? 3 : 1) * p.words + p.cnt + p.ovf + p.tmp;
+  return p;
+}
+
+}  // namespace
+
+extern "C" size_t pfsgnn_schedule_plan_args_bytes(void) { return sizeof(pfsgnn_schedule_plan_args); }
+
+extern "C" size_t pfsgnn_schedule_plan_ws_bytes(int G, int NF, int NC, long long E) {
+  if (G <= 0 || NF <= 0 || NC <= 0 || E < 0 || E >= (1ll << 31) ||
+      (long long)G * NF >= (1ll << 31) - 1 || (E == 0 && (long long)G * NF * NC >= (1ll << 31)))
+    return 0;
+  return plan_ws(G, NF, NC, E).total;
+}
+
+extern "C" int pfsgnn_schedule_plan(const pfsgnn_schedule_plan_args* a, void* ws, size_t ws_bytes,
+                                    void* stream) {
+  const char* where = "pfsgnn_schedule_plan";
+  PF_REQUIRE(a, where, "null argument struct");
+  const bool any_csr = a->src_p || a->tgt_p || a->user_of || a->fib_ptr || a->cls_ord || a->cls_ptr;
+  const bool complete = a->mode != -1 || a->perm;
+  PF_REQUIRE(!(complete && any_csr), where,
+             "both batch forms: a complete batch (mode 0..2, perm) leaves the CSR arrays NULL, a "
+             "general batch sets mode = -1 and no perm");
+  PF_REQUIRE(complete || any_csr, where,
+             "neither batch form: mode = -1 needs the CSR arrays of pfsgnn_sparse_layout");
+  if (complete) {
+    PF_REQUIRE(a->mode >= 0 && a->mode <= 2, where, "mode must be 0 (perm), 1 or 2");
+    PF_REQUIRE(a->mode != 0 || a->perm, where, "mode 0 needs perm");
+  } else {
+    PF_REQUIRE(a->src_p && a->tgt_p && a->user_of && a->fib_ptr && a->cls_ord && a->cls_ptr, where,
+               "the CSR form needs src_p, tgt_p, user_of, fib_ptr, cls_ord and cls_ptr");
+  }
+  PF_REQUIRE(a->visits && a->start && a->used && a->idle && a->n_hard && a->completeness &&
+                 a->utility && a->over && a->worst && a->cut && a->seg_ptr,
+             where, "null output (only seg_edge and seg_start may be NULL)");
+  PF_REQUIRE(a->ci && a->visits_in, where, "null input (ci, visits_in)");
+  PF_REQUIRE(a->seg_cap >= 0, where, "seg_cap must be >= 0");
+  PF_REQUIRE(a->seg_cap == 0 || (a->seg_edge && a->seg_start), where,
+             "seg_cap > 0 needs seg_edge and seg_start");
+  PF_REQUIRE(a->cap == 0 || a->cap == 1, where, "cap must be 0 or 1");
+  const int G = a->G, NF = a->NF, NC = a->NC;
+  PF_REQUIRE(G > 0 && NF > 0 && NC > 0 && (complete || a->E > 0), where,
+             "need G > 0, NF > 0, NC > 0 (and E > 0 in the CSR form)");
+  const long long NS = (long long)G * NF, NT = (long long)G * NC;
+  const long long E = complete ? NS * NC : a->E;
+  PF_REQUIRE(E < (1ll << 31) && NS < (1ll << 31) - 1 && NT < (1ll << 31), where,
+             "E too large for int32 edge ids (E, G*NF, G*NC < 2^31)");
+  const PlanWs p = plan_ws(G, NF, NC, complete ? 0 : E);
+  PF_REQUIRE(ws && ws_bytes >= p.total, where,
+             "workspace too small (pfsgnn_schedule_plan_ws_bytes)");
+  hipStream_t st = as_stream(stream);
+  char* wp = static_cast<char*>(ws);
+  int* keyA = reinterpret_cast<int*>(wp);
+  int* keyB = complete ? nullptr : reinterpret_cast<int*>(wp + p.words);
+  int* pord = complete ? nullptr : reinterpret_cast<int*>(wp + 2 * p.words);
+  wp += (complete ? 1 : 3) * p.words;
+  long long* cnt = reinterpret_cast<long long*>(wp);
+  int* ovf = reinterpret_cast<int*>(wp + p.cnt);
+  void* tmp = wp + p.cnt + p.ovf;
+  int* w = keyA;   // (general: the sort's input keys are dead once it has run)
+  const bool fill = a->seg_cap > 0;
+  PlanOut o{a->visits, a->start, a->used, a->idle, cnt, ovf, a->seg_ptr, a->seg_cap,
+            a->seg_edge, a->seg_start};
+  const unsigned egrid = (unsigned)std::max<long long>(1, std::min<long long>((E + 255) / 256, 8192));
+  if (!complete) {
+    hipLaunchKernelGGL(k_plan_keys, dim3(egrid), dim3(256), 0, st, E, a->src_p, a->cls_ord, keyA);
+    size_t tb = p.tmp;
+    if (hipcub::DeviceRadixSort::SortPairs(tmp, tb, keyA, keyB, a->cls_ord, pord, (int)E, 0,
+                                           plan_key_bits(NS), st) != hipSuccess)
+      return pf::fail(where, "radix sort (plan order)");
+    hipLaunchKernelGGL(k_plan_class<true>, dim3((unsigned)NT), dim3(256), 0, st, NF, NC, (int)NT,
+                       -1, nullptr, a->cls_ord, a->cls_ptr, a->user_of, a->ci, a->nfields, a->cap,
+                       a->visits_in, w, a->n_hard, a->completeness, a->cut);
+    hipLaunchKernelGGL(k_plan_fiber_csr<false>, dim3((unsigned)((NS + 3) / 4)), dim3(256), 0, st,
+                       NS, a->fib_ptr, pord, a->tgt_p, a->user_of, w, a->ci, a->total_time, o);
+  } else {
+    const int NFB = (NF + 255) / 256;
+    hipLaunchKernelGGL(k_plan_class<false>, dim3((unsigned)NT), dim3(256), 0, st, NF, NC, (int)NT,
+                       a->mode, a->perm, nullptr, nullptr, nullptr, a->ci, a->nfields, a->cap,
+                       a->visits_in, w, a->n_hard, a->completeness, a->cut);
+    hipLaunchKernelGGL(k_plan_fiber<false>, dim3((unsigned)(G * NFB)), dim3(256), 0, st, NF, NC,
+                       NFB, NS, a->mode, a->perm, w, a->ci, a->total_time, o);
+  }
+  hipLaunchKernelGGL(k_plan_finish, dim3(G), dim3(256), 0, st, NF, NC, a->completeness, a->used,
+                     ovf, a->utility, a->over, a->worst);
+  {
+    size_t tb = p.tmp;
+    if (hipcub::DeviceScan::ExclusiveSum(tmp, tb, cnt, a->seg_ptr, (int)(NS + 1), st) != hipSuccess)
+      return pf::fail(where, "scan (segment offsets)");
+  }
+  if (fill) {
+    if (!complete) {
+      hipLaunchKernelGGL(k_plan_fiber_csr<true>, dim3((unsigned)((NS + 3) / 4)), dim3(256), 0, st,
+                         NS, a->fib_ptr, pord, a->tgt_p, a->user_of, w, a->ci, a->total_time, o);
+    } else {
+      const int NFB = (NF + 255) / 256;
+      hipLaunchKernelGGL(k_plan_fiber<true>, dim3((unsigned)(G * NFB)), dim3(256), 0, st, NF, NC,
+                         NFB, NS, a->mode, a->perm, w, a->ci, a->total_time, o);
+    }
+  }
   return pf::check_launch(where);
 }

@@ -10,6 +10,7 @@ from .native import NativeUnavailable, HipBackend, set_edge_path, get_edge_path 
 from .gnn import (BipartiteData, Loader, Batch, MLP, EdgeModel, SModel, TModel,  # noqa: F401
                   GlobalModel, Block, GNN)
 from .train import softfloor, loss_function, hard_schedule, HardSchedule, BudgetSchedule, TrainLoop  # noqa: F401
+from .train import observing_plan, ObservingPlan  # noqa: F401
 from .optim import FusedAdam  # noqa: F401
 
 __version__ = "0.1.0"

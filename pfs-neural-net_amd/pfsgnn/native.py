@@ -241,6 +241,18 @@ class ScheduleBudgetArgs(ctypes.Structure):
                         "worst", "quot", "phase"))
 
 
+class PlanArgs(ctypes.Structure):
+    """pfsgnn_schedule_plan_args: the observing plan of an integer schedule --
+    class caps, fiber timelines, the target list -- of a complete batch (mode,
+    perm) or a general one (mode -1 and pfsgnn_sparse_layout's CSR arrays)."""
+    _fields_ = ([("G", I), ("NF", I), ("NC", I), ("mode", I)] + _ptrs("perm") + [("E", LL)]
+                + _ptrs("src_p", "tgt_p", "user_of", "fib_ptr", "cls_ord", "cls_ptr", "ci")
+                + [("total_time", FL), ("nfields", FL)] + _ptrs("visits_in")
+                + [("cap", I), ("seg_cap", LL)]
+                + _ptrs("visits", "start", "used", "idle", "n_hard", "completeness", "utility",
+                        "over", "worst", "cut", "seg_ptr", "seg_edge", "seg_start"))
+
+
 class CopyJob(ctypes.Structure):
     """pfsgnn_copy_job: n 4-byte words from src to dst."""
     _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("n", LL)]
@@ -368,6 +380,9 @@ _SIGS = {
     "pfsgnn_schedule_budget_max_nc": ([], I),
     "pfsgnn_schedule_budget_ws_bytes": ([I, I, I, LL], SZ),
     "pfsgnn_schedule_budget": ([ctypes.POINTER(ScheduleBudgetArgs), P, SZ, P], I),
+    "pfsgnn_schedule_plan_args_bytes": ([], SZ),
+    "pfsgnn_schedule_plan_ws_bytes": ([I, I, I, LL], SZ),
+    "pfsgnn_schedule_plan": ([ctypes.POINTER(PlanArgs), P, SZ, P], I),
 }
 for _op, _cls in EDGE_ARGS.items():
     _SIGS["pfsgnn_" + _op] = ([ctypes.POINTER(_cls), P, SZ, P], I)
@@ -408,7 +423,8 @@ def lib():
         sizes += [("pfsgnn_edge_args_bytes", (op,), cls) for op, cls in enumerate(EDGE_ARGS.values())]
         sizes += [("pfsgnn_train_record_hard_args_bytes", (), TrainRecordHardArgs),
                   ("pfsgnn_schedule_args_bytes", (), ScheduleArgs),
-                  ("pfsgnn_schedule_budget_args_bytes", (), ScheduleBudgetArgs)]
+                  ("pfsgnn_schedule_budget_args_bytes", (), ScheduleBudgetArgs),
+                  ("pfsgnn_schedule_plan_args_bytes", (), PlanArgs)]
         for query, qargs, cls in sizes:
             got, call = getattr(L, query)(*qargs), f"{query}({', '.join(map(str, qargs))})"
             if got != ctypes.sizeof(cls):
@@ -1704,6 +1720,69 @@ class HipBackend:
         need = lib().pfsgnn_schedule_budget_ws_bytes(d.G, d.NF, d.NC, 0 if sl is None else sl.EP)
         ws, wsb = self._wsargs(d, need)
         _call("pfsgnn_schedule_budget", ctypes.byref(a), ws, wsb, _stream())
+        return out
+
+    PLAN_FIELDS = ("visits", "start", "used", "idle", "n_hard", "completeness", "utility", "over",
+                   "worst", "cut", "seg_ptr")
+
+    def schedule_plan(self, d, ci, visits_in, total_time, nfields, *, mode=1, perm=None, sp=None,
+                      cap=True, seg_edge=None, seg_start=None, out=None):
+        """The observing plan of an integer schedule (pfsgnn_schedule_plan) ->
+        (visits [E] int32, start [E], used [NS], idle [NS], n [NT] int32,
+        completeness [NT], utility [G], over [G] int32, worst [G], cut [NT] int64,
+        seg_ptr [NS + 1] int64); per-edge tensors in the caller's edge order.
+        ``visits_in`` [E] int32 in the caller's order.  A complete batch gives
+        ``mode`` / ``perm``; a general one its ``sparse.SparseGeo`` as ``sp``
+        (``d.sp`` by default; a complete graph laid out by ``sparse_layout`` runs
+        through the CSR form when its geo is passed).  ``seg_edge`` (int32) and
+        ``seg_start`` (fp32), of equal length, receive the target list's
+        entries below their length; without them the call only counts.
+        ``out``: the eleven tensors to write into."""
+        sp = d.sp if sp is None else sp
+        E = d.E if sp is None else sp.E
+        i32 = dict(dtype=torch.int32, device=self.device)
+        i64 = dict(dtype=torch.int64, device=self.device)
+        if out is None:
+            out = (torch.empty(E, **i32), self.empty(E), self.empty(d.NS), self.empty(d.NS),
+                   torch.empty(d.NT, **i32), self.empty(d.NT), self.empty(d.G),
+                   torch.empty(d.G, **i32), self.empty(d.G), torch.empty(d.NT, **i64),
+                   torch.empty(d.NS + 1, **i64))
+        visits, start, used, idle, n_hard, comp, utility, over, worst, cut, seg_ptr = out
+        assert visits.dtype == n_hard.dtype == over.dtype == torch.int32
+        assert cut.dtype == seg_ptr.dtype == torch.int64
+        self._chk(start, used, idle, comp, utility, worst, seg_start)
+        assert all(t.is_cuda and t.is_contiguous() for t in (visits, n_hard, over, cut, seg_ptr))
+        assert visits.numel() == start.numel() == E and used.numel() == idle.numel() == d.NS
+        assert n_hard.numel() == comp.numel() == cut.numel() == d.NT
+        assert min(utility.numel(), over.numel(), worst.numel()) == d.G
+        assert seg_ptr.numel() == d.NS + 1
+        assert (visits_in.dtype == torch.int32 and visits_in.is_cuda and visits_in.is_contiguous()
+                and visits_in.numel() == E)
+        ci = ci.contiguous()
+        assert ci.numel() >= 2 * d.NT
+        a = PlanArgs(G=d.G, NF=d.NF, NC=d.NC, cap=int(bool(cap)))
+        if sp is not None:
+            a.mode, a.E = -1, E
+            for k in ("src_p", "tgt_p", "user_of", "fib_ptr", "cls_ord", "cls_ptr"):
+                setattr(a, k, getattr(sp, k).data_ptr())
+        else:
+            a.mode = int(mode)
+            if perm is not None:
+                assert perm.dtype == torch.int32 and perm.is_cuda and perm.numel() == E
+                a.perm = perm.data_ptr()
+        a.ci, a.visits_in = ci.data_ptr(), visits_in.data_ptr()
+        a.total_time, a.nfields = float(total_time), float(nfields)
+        if seg_edge is not None or seg_start is not None:
+            assert seg_edge.dtype == torch.int32 and seg_edge.is_cuda and seg_edge.is_contiguous()
+            assert seg_edge.numel() == seg_start.numel()
+            a.seg_cap = seg_edge.numel()
+            if a.seg_cap:
+                a.seg_edge, a.seg_start = seg_edge.data_ptr(), seg_start.data_ptr()
+        for k, v in zip(self.PLAN_FIELDS, out):
+            setattr(a, k, v.data_ptr())
+        need = lib().pfsgnn_schedule_plan_ws_bytes(d.G, d.NF, d.NC, 0 if sp is None else E)
+        ws, wsb = self._wsargs(None, need)
+        _call("pfsgnn_schedule_plan", ctypes.byref(a), ws, wsb, _stream())
         return out
 
     def loss_finalize(self, d, n_prime, fiber_time, tvar, ci, pclass, pfiber, total_time, nfields,

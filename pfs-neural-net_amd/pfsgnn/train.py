@@ -377,6 +377,160 @@ def _hard_schedule(graph, class_info, rounding, gnn, out, time=None):
     return (BudgetSchedule if budget else HardSchedule)(*res)
 
 
+# ---------------------------------------------------------------- observing plan
+ObservingPlan = collections.namedtuple(
+    "ObservingPlan", "visits start used idle n completeness utility over worst cut seg_ptr "
+                     "seg_edge seg_start")
+
+
+def _plan_geometry(graph, F=None):
+    """(Dims, Layout) of an input batch or of a ``GNN.forward`` output: only
+    ``edge_index`` and the node counts matter, through the cached layout."""
+    pf = graph.__dict__.get("_pf")
+    if pf is not None:
+        return pf[1], pf[2]
+    F = int(graph.x_e.size(1)) if F is None else int(F)
+    return _gnn.geometry(graph.x_s, graph.x_t, graph.x_u, graph.edge_index, F)
+
+
+def observing_plan(graph, class_info, visits, *, cap=True, segments=True, _F=None):
+    """From an integer schedule to the plan an observer runs (the definition is
+    pfsgnn_schedule_plan's in include/pfsgnn.h): visits capped per class by the
+    galaxies it has per field (train.py:41's ``N_i``, which train.py:57-58 only
+    penalises), each fiber's classes laid end to end (train.py:256-261's
+    ``cumsum`` / ``left``) and every single exposure at ``left + m * class_req``
+    (train.py:283-284).
+
+    ``graph`` is the input batch or the output of ``GNN.forward`` -- only
+    ``edge_index`` and the node counts are used; complete batches in any edge
+    order and every general batch (the composed path included).  ``visits`` is
+    any int tensor or array of E entries in the caller's edge order, e.g.
+    ``hard_schedule(...).visits`` or ``TrainLoop.hard_best()["visits"]``.
+    ``cap=True`` trims a class whose visits exceed ``floor(N_c / NFIELDS)`` to
+    that number, max-min fair, ties to the lower (fiber, edge position).
+
+    Returns an ``ObservingPlan`` of device tensors: ``visits`` [E] int32 and
+    ``start`` [E] (the time at which the fiber turns to the edge's class) in the
+    caller's edge order; ``used``, ``idle`` [NS] (``TOTAL_TIME - used``: negative
+    for a fiber that is over); ``n`` [NT] int32, ``completeness`` [NT],
+    ``utility``, ``over``, ``worst`` [G] as ``hard_schedule``'s; ``cut`` [NT]
+    int64, the visits the cap removed; ``seg_ptr`` [NS + 1] int64, and the
+    target list ``seg_edge`` (int32, the caller's edge) / ``seg_start`` of
+    ``seg_ptr[-1]`` entries: fiber f's exposures are ``seg_ptr[f] :
+    seg_ptr[f + 1]``, in the order it takes them.  With ``segments=True`` the
+    wrapper runs the op once to count, reads ``seg_ptr[-1]`` -- the ONE host
+    synchronisation -- allocates, and runs it again.  With ``segments=False``
+    ``seg_edge`` and ``seg_start`` are None and nothing synchronises (the call
+    can be captured)."""
+    d, lay = _plan_geometry(graph, _F)
+    ci = _class_info_cm(class_info, d)
+    vis = torch.as_tensor(visits)
+    if vis.is_floating_point() or vis.dtype == torch.bool or vis.is_complex():
+        raise ValueError(f"visits must be an integer tensor or array; got {vis.dtype}")
+    if vis.numel() != d.E:
+        raise ValueError(f"visits has {vis.numel()} entries for {d.E} edges")
+    if vis.dtype != torch.int32:
+        vis = vis.clamp(-(2 ** 31), 2 ** 31 - 1).to(torch.int32)
+    vis = vis.to(ci.device).reshape(-1).contiguous()
+    be = backend()
+    total, nfields = float(config.TOTAL_TIME), float(config.NFIELDS)
+    if hasattr(be, "schedule_plan"):
+        kw = dict(sp=lay.sp) if lay.sp is not None else dict(mode=lay.mode, perm=lay.perm)
+        out = be.schedule_plan(d, ci, vis, total, nfields, cap=cap, **kw)
+        seg_edge = seg_start = None
+        if segments:
+            count = int(out[-1][-1])                # the one host synchronisation
+            seg_edge = torch.empty(count, dtype=torch.int32, device=ci.device)
+            seg_start = torch.empty(count, dtype=torch.float32, device=ci.device)
+            if count:
+                be.schedule_plan(d, ci, vis, total, nfields, cap=cap, seg_edge=seg_edge,
+                                 seg_start=seg_start, out=out, **kw)
+        return ObservingPlan(*out, seg_edge, seg_start)
+    # a backend without the op (a CPU emulation of the op set): host restatement
+    res = _observing_plan_host(vis.cpu().numpy(), graph.edge_index.cpu().numpy(),
+                               ci.cpu().numpy(), total, nfields, d.G, d.NF, d.NC, cap, segments)
+    return ObservingPlan(*(None if r is None else torch.from_numpy(r).to(ci.device) for r in res))
+
+
+def _observing_plan_host(visits, ei, ci, total_time, nfields, G, NF, NC, cap, segments):
+    """pfsgnn_schedule_plan on the host, for backends without the op: sorts and
+    segment sums in numpy, a Python loop only over the trimmed classes and the
+    fibers.  ``ci`` fp32 [2, NT] -> ObservingPlan's fields as numpy arrays."""
+    NS, NT = G * NF, G * NC
+    src, tgt = ei[0].astype(np.int64), ei[1].astype(np.int64)
+    E = src.size
+    pos = np.arange(E)
+    T, N = ci[0].astype(np.float32), ci[1].astype(np.float32)
+    Te = T[tgt]
+    live = (Te > 0) & np.isfinite(Te)
+    w = np.where(live, np.clip(visits.astype(np.int64), 0, 1 << 24), 0)
+    with np.errstate(all="ignore"):
+        q = N / np.float32(nfields)
+    S = np.zeros(NT, np.int64)
+    np.add.at(S, tgt, w)
+    cut = np.zeros(NT, np.int64)
+    if cap:
+        bad = np.isnan(q) | (q < 0)
+        nocap = ~bad & (q >= np.float32(2.0 ** 31))
+        capc = np.where(bad | nocap, 0, np.floor(np.where(bad | nocap, 0, q))).astype(np.int64)
+        byclass = np.lexsort((pos, src, tgt))
+        cptr = np.searchsorted(tgt[byclass], np.arange(NT + 1))
+        for c in np.nonzero(~nocap & (S > capc))[0]:
+            e = byclass[cptr[c]:cptr[c + 1]]          # ascending (src, position)
+            wc = w[e]
+            ws = np.sort(wc)
+            pre = np.concatenate([[0], np.cumsum(ws)])
+            # f(L) = sum min(w, L) = pre[k] + L (n - k), k = #{w <= L}
+            lo, hi = 0, int(ws[-1])
+            while hi - lo > 1:
+                mid = (lo + hi) // 2
+                k = np.searchsorted(ws, mid, side="right")
+                if pre[k] + mid * (ws.size - k) <= capc[c]:
+                    lo = mid
+                else:
+                    hi = mid
+            k = np.searchsorted(ws, lo, side="right")
+            rem = int(capc[c] - (pre[k] + lo * (ws.size - k)))
+            above = np.nonzero(wc > lo)[0]
+            wc = np.minimum(wc, lo)
+            wc[above[:rem]] += 1
+            w[e] = wc
+            cut[c] = S[c] - capc[c]
+            S[c] = capc[c]
+    order = np.lexsort((pos, tgt, src))               # the plan order, fiber by fiber
+    fptr = np.searchsorted(src[order], np.arange(NS + 1))
+    wo = w[order]
+    To = Te[order].astype(np.float64)
+    dur = np.where(wo > 0, wo * np.where(wo > 0, To, 0.0), 0.0)
+    start_o = np.zeros(E)
+    tot = np.zeros(NS)
+    for f in range(NS):
+        a, b = fptr[f], fptr[f + 1]
+        if b > a:
+            cs = np.cumsum(dur[a:b])
+            start_o[a + 1:b] = cs[:-1]
+            tot[f] = cs[-1]
+    start = np.empty(E, np.float32)
+    start[order] = start_o.astype(np.float32)
+    total = float(np.float32(total_time))
+    used, idle = tot.astype(np.float32), (total - tot).astype(np.float32)
+    cnt = np.zeros(NS, np.int64)
+    np.add.at(cnt, src, w)
+    seg_ptr = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
+    seg_edge = seg_start = None
+    if segments:
+        seg_edge = np.repeat(order, wo).astype(np.int32)
+        first = np.cumsum(wo) - wo
+        m = np.arange(int(wo.sum())) - np.repeat(first, wo)
+        seg_start = (np.repeat(start_o, wo) + m * np.repeat(To, wo)).astype(np.float32)
+    n = S.astype(np.int32)
+    with np.errstate(all="ignore"):
+        comp = n.astype(np.float32) / q
+    return (w.astype(np.int32), start, used, idle, n, comp, comp.reshape(G, NC).min(axis=1),
+            (tot.reshape(G, NF) > total).sum(axis=1).astype(np.int32),
+            used.reshape(G, NF).max(axis=1), cut, seg_ptr, seg_edge, seg_start)
+
+
 # ---------------------------------------------------------------- training
 def complete_graph(class_info, nfibers, fdim, lo=2.0, hi=10.0):
     """train.py:88-104: fiber counter x_s, class_info x_t, fiber-major complete
@@ -694,6 +848,17 @@ class TrainLoop:
         return dict(utility=float(self._best_hard_utility), epoch=int(self._best_hard_epoch),
                     visits=visits.cpu().numpy(), fiber_time=fiber_time.cpu().numpy(),
                     completion=completion.cpu().numpy())
+
+    def plan(self, cap=True, segments=True):
+        """The observing plan (``observing_plan``) of the best integer schedule so
+        far (``track_hard``; with ``track_hard="budget"`` the best executable
+        one): its visits go from the device buffer straight into the op.  Before
+        any epoch has had a positive hard utility the best visits are all 0 and
+        the plan is empty."""
+        if not self.track_hard:
+            raise ValueError("plan() needs TrainLoop(..., track_hard=True)")
+        return observing_plan(self.graph, self.class_info, self._best_hard[0], cap=cap,
+                              segments=segments, _F=getattr(self.gnn, "Fdim", None))
 
     def _optim_state(self, tensors):
         """optimizer.state_dict() with its state tensors replaced by
