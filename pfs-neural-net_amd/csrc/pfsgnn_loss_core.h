@@ -150,6 +150,14 @@ __device__ __forceinline__ const float* dec_base(const DecW<F>& d) {
   asm volatile("" : "+v"(lo));
   return d.w + lo;
 }
+// EdgeTime on the staged weights (DecW's layout: Wd1 | bd1 | Wd2 | bd2)
+template <int F>
+__device__ __forceinline__ float edge_time(const float (&x)[F], const DecW<F>& dw, float scale) {
+  EdgeTime<F> L;
+  const float* dwp = dec_base(dw);
+  L.run(x, dwp, dwp + F * F, dwp + F * F + F, dwp + F * F + 2 * F, scale);
+  return L.time;
+}
 
 // ---- the dense loss kernels' iteration (pfsgnn_loss.hip, pfsgnn_schedule.hip):
 // EdgeGeo's block -> (graph, 64-fiber group, class split), lane = fiber, wave w
@@ -204,6 +212,13 @@ __device__ __forceinline__ long long user_index(long long k, int NF, int NC, int
   const long long g = gc / NC, c = gc - g * NC;
   return (g * NF + f) * NC + c;
 }
+// the same for a kernel that walks (g, c, f) and has the fiber-major index at
+// hand: no divisions.  (user_index is not built on it: its early returns
+// compile to other code in k_to_canonical / k_from_canonical than a select)
+__device__ __forceinline__ long long caller_pos(int mode, long long k, long long fiber_major,
+                                                const int32_t* __restrict__ perm) {
+  return mode == 2 ? k : (mode == 1 ? fiber_major : (long long)perm[k]);
+}
 
 
 // the loss kernels' grid: class splits to about PFSGNN_LOSS_BLOCKS blocks
@@ -238,7 +253,7 @@ inline EdgeGeo loss_geo(int G, int NF, int NC) {
   const long long EP = geo.E, NS = geo.NS;                                             \
   const long long cn0 = (long long)gg * NC;                                            \
   const long long p0 = (long long)pb + 16ll * k0 + lane;                               \
-  (void)NS; (void)t;
+  (void)NS; (void)t; (void)nit; (void)EP; (void)cn0;
 
 // the lane's edge of one iteration: channel rows, class byte, caller edge id
 // (steps beyond the split load nothing: class 0xFF, edge -1, rows 0)
@@ -257,6 +272,22 @@ struct SlEdge {
     r.pos = r.in ? pos_user[p] : -1;                                                   \
     _Pragma("unroll") for (int k = 0; k < F; ++k)                                      \
       r.y[k] = r.in ? y[(long long)k * EP + p] : 0.f;                                  \
+    return r;                                                                          \
+  };
+// the same with the position opaque per iteration, and the rows addressed from
+// it: the compiler would otherwise keep one 64-bit row address per channel
+// across the loop (2 F VGPRs).  pfsgnn_schedule.hip's time pass uses it
+#define SLL_LOAD_OPAQUE_DECL(F)                                                        \
+  auto load = [&](int i) {                                                             \
+    SlEdge<F> r;                                                                       \
+    r.in = k0 + 4 * i + q4 < k1;                                                       \
+    long long p = p0 + 64ll * i;                                                       \
+    asm volatile("" : "+v"(p));                                                        \
+    r.cls = r.in ? (int)sl.cls[p] : 0xFF;                                              \
+    r.pos = r.in ? pos_user[p] : -1;                                                   \
+    const float* yp = y + p;                                                           \
+    _Pragma("unroll") for (int k = 0; k < F; ++k)                                      \
+      r.y[k] = r.in ? yp[(long long)k * EP] : 0.f;                                     \
     return r;                                                                          \
   };
 // validity and the class clamped to 0 (padding 0xFF, steps beyond the split and

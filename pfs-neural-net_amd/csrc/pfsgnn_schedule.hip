@@ -12,11 +12,12 @@
 //   completeness_c = n_c / (N_c / nfields); utility_g = min_c; over_g = #{f:
 //   fiber_time_f > total_time}; worst_g = max_f fiber_time_f
 //
-// No noise, no sharpness, no seed.  The dense kernel has k_loss_fwd's grid and
-// ownership (lane = fiber, 4 waves over the classes of a split, the prefetch
-// ring), the sliced one ksl_loss_fwd's (a lane owns an edge, four steps per
-// iteration); one finish launch per graph reduces the int32 class partials and
-// the fiber partials.  Nothing allocates, synchronises or uses float atomics
+// No noise, no sharpness, no seed.  Launches: the per-edge time pass of the
+// batch's layout (dense_time_pass / sliced_time_pass below, which the budget's
+// quotient pass shares) with the visit count as its sink -- k_schedule /
+// ksl_schedule; then one finish launch per graph, which reduces the int32
+// class partials and the fiber partials and ends in graph_summary (which the
+// plan's finish shares).  Nothing allocates, synchronises or uses float atomics
 // (the sliced class counts are LDS integer adds: order-free, so reproducible).
 #include "pfsgnn_common.h"
 #include "pfsgnn_loss_core.h"
@@ -33,15 +34,6 @@ namespace {
 using pfm::SlGeo;
 constexpr int MAXC = pfm::SL_MAX_NC;
 
-// wave_sum (pfsgnn_common.h) on int32: every lane gets the total
-__device__ __forceinline__ int wave_isum(int v) {
-  v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, false);
-  v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xF, 0xF, false);
-  v += __builtin_amdgcn_update_dpp(0, v, 0x141, 0xF, 0xF, false);
-  v += __builtin_amdgcn_update_dpp(0, v, 0x140, 0xF, 0xF, false);
-  return (__builtin_amdgcn_readlane(v, 0) + __builtin_amdgcn_readlane(v, 16)) +
-         (__builtin_amdgcn_readlane(v, 32) + __builtin_amdgcn_readlane(v, 48));
-}
 // sum over the lane's row of 16 lanes, in every lane of the row
 __device__ __forceinline__ int row_isum16(int v) {
   v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, false);
@@ -49,6 +41,75 @@ __device__ __forceinline__ int row_isum16(int v) {
   v += __builtin_amdgcn_update_dpp(0, v, 0x141, 0xF, 0xF, false);
   v += __builtin_amdgcn_update_dpp(0, v, 0x140, 0xF, 0xF, false);
   return v;
+}
+// wave_sum (pfsgnn_common.h) on int32: every lane gets the total
+__device__ __forceinline__ int wave_isum(int v) {
+  v = row_isum16(v);
+  return (__builtin_amdgcn_readlane(v, 0) + __builtin_amdgcn_readlane(v, 16)) +
+         (__builtin_amdgcn_readlane(v, 32) + __builtin_amdgcn_readlane(v, 48));
+}
+
+// a class time that gives its edges no visits: zero, negative, infinite or NaN
+__device__ __forceinline__ bool inert_T(float T) { return !(T > 0.f) || !(T < INFINITY); }
+
+// ---- the per-edge time pass, once per layout.  A kernel opens with its
+// layout's prologue and passes on the block's place; the pass stages
+// decoder_e's weights in LDS, walks the block's edges one load ahead, applies
+// the input affine and EdgeTime, and hands every edge's time to the kernel's
+// sink, in uniform control flow (a sink may use wave-wide operations).  What a
+// kernel does with the time -- and its epilogue -- is its own; the passes know
+// no kernel.
+//
+// Dense: k_loss_fwd's grid and ownership (lane = fiber, 4 waves over the
+// classes of a split, the prefetch ring); gg .. wave are EDGE_PROLOGUE's.
+// sink(time, fvalid, cn, e, eu): the lane's fiber exists, the class's index
+// into ci, the edge's canonical index and its fiber-major one.
+template <int F, class Sink>
+__device__ __forceinline__ void dense_time_pass(
+    const EdgeGeo& geo, int gg, int f, bool fvalid, int c0, int c1, int wave,
+    const float* __restrict__ y, const float* __restrict__ sc, const float* __restrict__ sh,
+    const float* __restrict__ Wd1, const float* __restrict__ bd1, const float* __restrict__ Wd2,
+    const float* __restrict__ bd2, float scale, Sink sink) {
+  const long long E = geo.E, n = (long long)gg * geo.NF + (fvalid ? f : 0);
+  __shared__ __attribute__((aligned(16))) DecW<F> dw;
+  dw.load(Wd1, bd1, Wd2, bd2);
+  __syncthreads();
+  Y_PREFETCH_DECL(F)
+  CLASS_LOOP_BEGIN
+    float x[F];
+    Y_TAKE(F, x)
+    sink(edge_time<F>(x, dw, scale), fvalid, cn, e, eu);
+  CLASS_LOOP_END
+}
+
+// Sliced: ksl_loss_fwd's grid and ownership (a lane owns an edge, four steps
+// per iteration), with the loader whose position is opaque; gg .. p0 are
+// SLL_PROLOGUE's.  sink(time, ev, cl, cn, edge, slot): SLL_STEP's validity,
+// clamped class and index into ci, the SlEdge and its slot in the sliced
+// layout.  The barrier after the staging also covers what the kernel put in
+// LDS before the call.
+template <int F, class Sink>
+__device__ __forceinline__ void sliced_time_pass(
+    const EdgeGeo& geo, const SlGeo& sl, int gg, int fib, int q4, int k0, int k1, long long p0,
+    const int* __restrict__ pos_user, const float* __restrict__ y, const float* __restrict__ sc,
+    const float* __restrict__ sh, const float* __restrict__ Wd1, const float* __restrict__ bd1,
+    const float* __restrict__ Wd2, const float* __restrict__ bd2, float scale, Sink sink) {
+  const int NC = geo.NC, nit = (k1 - k0 + 3) >> 2;
+  const long long EP = geo.E, cn0 = (long long)gg * NC;
+  __shared__ __attribute__((aligned(16))) DecW<F> dw;
+  dw.load(Wd1, bd1, Wd2, bd2);
+  __syncthreads();
+  SLL_LOAD_OPAQUE_DECL(F)
+  SlEdge<F> cur = load(0);
+  for (int i = 0; i < nit; ++i) {
+    const SlEdge<F> nxt = load(i + 1);
+    SLL_STEP(cur)
+    float x[F];
+#pragma unroll
+    for (int k = 0; k < F; ++k) x[k] = sc ? fmaf(cur.y[k], sc[k], sh[k]) : cur.y[k];
+    sink(edge_time<F>(x, dw, scale), ev, cl, cn, cur, p0 + 64ll * i);
+    cur = nxt;
+  }
 }
 
 // the visit count of an edge and its time; the product is rounded to fp32 on
@@ -82,28 +143,17 @@ __global__ __launch_bounds__(256) void k_schedule(EdgeGeo geo, const float* __re
                                                   int* __restrict__ part) {
   EDGE_PROLOGUE
   __shared__ float scratch[4 * 64];
-  __shared__ __attribute__((aligned(16))) DecW<F> dw;
-  dw.load(Wd1, bd1, Wd2, bd2);
-  __syncthreads();
   float ft = 0.f;
-  Y_PREFETCH_DECL(F)
-  CLASS_LOOP_BEGIN
-    float x[F];
-    Y_TAKE(F, x)
-    EdgeTime<F> L;
-    const float* dwp = dec_base(dw);
-    L.run(x, dwp, dwp + F * F, dwp + F * F + F, dwp + F * F + 2 * F, scale);
-    const Visit h = hard_visit(L.time, ci[cn], rounding);
+  dense_time_pass<F>(geo, gg, f, fvalid, c0, c1, wave, y, sc, sh, Wd1, bd1, Wd2, bd2, scale,
+                     [&](float time, bool fvalid, long long cn, long long e, long long eu) {
+    const Visit h = hard_visit(time, ci[cn], rounding);
     const int vn = fvalid ? h.n : 0;
     ft += fvalid ? h.tt : 0.f;
-    if (fvalid) {
-      // the caller's edge: canonical, train.py's fiber-major, or a permutation
-      const long long u = mode == 2 ? e : (mode == 1 ? eu : (long long)perm[e]);
-      visits[u] = vn;
-    }
+    if (fvalid) visits[caller_pos(mode, e, eu, perm)] = vn;
     const int ns = wave_isum(vn);
+    const int c = (int)(cn - (long long)gg * geo.NC);
     if (lane == 0) part[((size_t)gg * geo.NFG + fg) * geo.NC + c] = ns;
-  CLASS_LOOP_END
+  });
   // fiber time: merge the 4 waves, KS-partial per fiber (k_loss_fwd's order)
   __syncthreads();
   scratch[wave * 64 + lane] = ft;
@@ -122,39 +172,15 @@ __global__ __launch_bounds__(256) void ksl_schedule(
     float* __restrict__ fiber_time, int* __restrict__ part) {
   SLL_PROLOGUE
   __shared__ int cnt[MAXC];
-  __shared__ __attribute__((aligned(16))) DecW<F> dw;
-  dw.load(Wd1, bd1, Wd2, bd2);
   for (int i = t; i < MAXC; i += PF_BLOCK) cnt[i] = 0;
-  __syncthreads();
   float ft = 0.f;
-  // SLL_LOAD_DECL with the position opaque per iteration: the compiler would
-  // otherwise keep one 64-bit row address per channel across the loop (2 F VGPRs)
-  auto load = [&](int i) {
-    SlEdge<F> r;
-    r.in = k0 + 4 * i + q4 < k1;
-    long long p = p0 + 64ll * i;
-    asm volatile("" : "+v"(p));
-    r.cls = r.in ? (int)sl.cls[p] : 0xFF;
-    r.pos = r.in ? pos_user[p] : -1;
-    const float* yp = y + p;
-#pragma unroll
-    for (int k = 0; k < F; ++k) r.y[k] = r.in ? yp[(long long)k * EP] : 0.f;
-    return r;
-  };
-  SlEdge<F> cur = load(0);
-  for (int i = 0; i < nit; ++i) {
-    const SlEdge<F> nxt = load(i + 1);
-    SLL_STEP(cur)
-    float x[F];
-#pragma unroll
-    for (int k = 0; k < F; ++k) x[k] = sc ? fmaf(cur.y[k], sc[k], sh[k]) : cur.y[k];
-    EdgeTime<F> L;
-    const float* dwp = dec_base(dw);
-    L.run(x, dwp, dwp + F * F, dwp + F * F + F, dwp + F * F + 2 * F, scale);
-    const Visit h = hard_visit(L.time, ci[cn], rounding);
+  sliced_time_pass<F>(geo, sl, gg, fib, q4, k0, k1, p0, pos_user, y, sc, sh, Wd1, bd1, Wd2, bd2,
+                      scale,
+                      [&](float time, bool ev, int cl, long long cn, const SlEdge<F>& ed, long long) {
+    const Visit h = hard_visit(time, ci[cn], rounding);
     const int vn = ev ? h.n : 0;
     ft += ev ? h.tt : 0.f;
-    if (ev) visits[cur.pos] = vn;
+    if (ev) visits[ed.pos] = vn;
     // class counts: LDS integer adds (order-free).  A row of 16 lanes whose
     // edges share one class (complete-like slices) adds its sum once.
     const uint64_t vm = __ballot(ev);
@@ -169,8 +195,7 @@ __global__ __launch_bounds__(256) void ksl_schedule(
         atomicAdd(&cnt[cl], vn);
       }
     }
-    cur = nxt;
-  }
+  });
   // fiber time: the four step groups of a fiber in fixed order, KS-partial per
   // global fiber (ksl_loss_fwd's order; 0 for a fiber without edges)
   {
@@ -186,6 +211,34 @@ __device__ __forceinline__ float nan_max(float a, float b) {
   return (a != a) ? a : ((b != b) ? b : (b > a ? b : a));
 }
 
+// a graph's summary from its block of 256 threads: utility = the minimum of
+// the threads' completeness minima (a NaN propagates, like torch.min), over =
+// the sum of their counts of fibers over total_time, worst = the maximum of
+// their fiber-time maxima (from 0; a NaN propagates)
+__device__ __forceinline__ void graph_summary(float mn, float mx, int ov, float* utility,
+                                              int* over, float* worst) {
+  const int g = blockIdx.x, t = threadIdx.x;
+  __shared__ float smin[256], smax[256];
+  __shared__ int sover[256];
+  smin[t] = mn;
+  smax[t] = mx;
+  sover[t] = ov;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (t < s) {
+      smin[t] = nan_min(smin[t], smin[t + s]);
+      smax[t] = nan_max(smax[t], smax[t + s]);
+      sover[t] += sover[t + s];
+    }
+    __syncthreads();
+  }
+  if (t == 0) {
+    utility[g] = smin[0];
+    over[g] = sover[0];
+    worst[g] = smax[0];
+  }
+}
+
 // one block per graph: the integer class reduce over the graph's bpg partial
 // rows (dense: one per 64-fiber group; sliced: one per block), completeness
 // and its minimum; the KS fiber partials in fixed order, the fibers over
@@ -196,8 +249,6 @@ __global__ __launch_bounds__(256) void k_schedule_finish(
     int* __restrict__ n_hard, float* __restrict__ fiber_time, float* __restrict__ completeness,
     float* __restrict__ utility, int* __restrict__ over, float* __restrict__ worst) {
   const int g = blockIdx.x, t = threadIdx.x;
-  __shared__ float smin[256], smax[256];
-  __shared__ int sover[256];
   __shared__ int cnt[256];
   float mn = INFINITY;
   // classes in chunks of 256; within a chunk of ncc classes the 256 threads form
@@ -242,60 +293,52 @@ __global__ __launch_bounds__(256) void k_schedule_finish(
     ov += s > total_time ? 1 : 0;
     mx = nan_max(mx, s);
   }
-  smin[t] = mn;
-  smax[t] = mx;
-  sover[t] = ov;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (t < s) {
-      smin[t] = nan_min(smin[t], smin[t + s]);
-      smax[t] = nan_max(smax[t], smax[t + s]);
-      sover[t] += sover[t + s];
-    }
-    __syncthreads();
-  }
-  if (t == 0) {
-    utility[g] = smin[0];
-    over[g] = sover[0];
-    worst[g] = smax[0];
-  }
+  graph_summary(mn, mx, ov, utility, over, worst);
 }
 
+// a bump allocator over the caller's workspace (256-byte aligned pieces); `used`
+// counts what was asked for, fitting or not: a pass with p = NULL sizes a layout
 struct Ws {
   char* p;
-  size_t left;
-  void* take(size_t bytes) {
-    const size_t b = align256(bytes);
+  size_t left, used = 0;
+  template <class T>
+  T* take(size_t n) {
+    const size_t b = align256(n * sizeof(T));
+    used += b;
     if (!p || b > left) return nullptr;
-    void* r = p;
+    T* r = reinterpret_cast<T*>(p);
     p += b;
     left -= b;
     return r;
   }
 };
 
-}  // namespace
+SlGeo sl_of(const pfsgnn_sliced_t& s) {
+  return SlGeo{s.fib, s.base, s.len, s.cls, s.pco, s.EP, s.E, s.maxdeg};
+}
 
-extern "C" size_t pfsgnn_schedule_args_bytes(void) { return sizeof(pfsgnn_schedule_args); }
-
-extern "C" int pfsgnn_schedule(const pfsgnn_schedule_args* a, void* ws, size_t ws_bytes,
-                               void* stream) {
-  const char* where = "pfsgnn_schedule";
-  PF_REQUIRE(a, where, "null argument struct");
-  PF_REQUIRE(!a->sl == !a->pos_user, where,
+// a complete batch's edge order
+int check_mode(const char* where, int mode, const int32_t* perm) {
+  PF_REQUIRE(mode >= 0 && mode <= 2, where, "mode must be 0 (perm), 1 or 2");
+  PF_REQUIRE(mode != 0 || perm, where, "mode 0 needs perm");
+  return 0;
+}
+// the batch of an op that reads the edge state: its form (sliced by sl and
+// pos_user, or complete by mode and perm), the decoder width, the dimensions
+// and what the layout's kernels can hold
+int check_batch(const char* where, int G, int NF, int NC, int F, const pfsgnn_sliced_t* sl,
+                const int* pos_user, int mode, const int32_t* perm) {
+  PF_REQUIRE(!sl == !pos_user, where,
              "sl and pos_user go together (both set: a sliced general batch; both NULL: complete)");
-  PF_REQUIRE(!(a->sl && a->perm), where,
+  PF_REQUIRE(!(sl && perm), where,
              "sl with perm: a sliced batch maps its edges by pos_user, mode and perm are the "
              "complete batch's");
-  PF_REQUIRE(a->sl || (a->mode >= 0 && a->mode <= 2), where, "mode must be 0 (perm), 1 or 2");
-  PF_REQUIRE(a->sl || a->mode != 0 || a->perm, where, "mode 0 needs perm");
-  PF_REQUIRE(a->rounding == 0 || a->rounding == 1, where, "rounding must be 0 (floor) or 1 (round)");
-  const int G = a->G, NF = a->NF, NC = a->NC, F = a->F;
+  if (int rc = sl ? 0 : check_mode(where, mode, perm)) return rc;
   PF_REQUIRE(F == 8 || F == 10 || F == 16, where, "unsupported Fdim (8, 10, 16)");
   PF_REQUIRE(G > 0 && NF > 0 && NC > 0, where, "need G > 0, NF > 0, NC > 0");
-  if (a->sl) {
-    const pfsgnn_sliced_t* s = a->sl;
-    PF_REQUIRE(s->fib && s->base && s->len && s->cls && s->EP > 0 && s->E > 0 && s->EP >= s->E,
+  if (sl) {
+    PF_REQUIRE(sl->fib && sl->base && sl->len && sl->cls && sl->EP > 0 && sl->E > 0 &&
+                   sl->EP >= sl->E,
                where, "bad sliced layout");
     int m = 0;
     if (pfsgnn_sliced_max_nc(F, &m) != 0 || m <= 0)
@@ -305,50 +348,51 @@ extern "C" int pfsgnn_schedule(const pfsgnn_schedule_args* a, void* ws, size_t w
   } else {
     PF_REQUIRE((long long)G * NF * NC < (1ll << 31), where, "E too large for int32 edge ids");
   }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" size_t pfsgnn_schedule_args_bytes(void) { return sizeof(pfsgnn_schedule_args); }
+
+extern "C" int pfsgnn_schedule(const pfsgnn_schedule_args* a, void* ws, size_t ws_bytes,
+                               void* stream) {
+  const char* where = "pfsgnn_schedule";
+  PF_REQUIRE(a, where, "null argument struct");
+  const int G = a->G, NF = a->NF, NC = a->NC, F = a->F;
+  if (int rc = check_batch(where, G, NF, NC, F, a->sl, a->pos_user, a->mode, a->perm)) return rc;
+  PF_REQUIRE(a->rounding == 0 || a->rounding == 1, where, "rounding must be 0 (floor) or 1 (round)");
   PF_REQUIRE(a->visits && a->n_hard && a->fiber_time && a->completeness && a->utility && a->over &&
                  a->worst,
              where, "null output");
   PF_REQUIRE(a->y && a->Wd1 && a->bd1 && a->Wd2 && a->bd2 && a->ci && (!a->sc == !a->sh), where,
              "null input (sc and sh go together)");
   hipStream_t st = as_stream(stream);
+  // class-partial rows per graph: a sliced block holds every class, the dense
+  // class splits own disjoint classes
+  const SlGeo sg = a->sl ? sl_of(*a->sl) : SlGeo{};
+  const EdgeGeo geo = a->sl ? pfm::sl_geo(G, NF, NC, sg) : loss_geo(G, NF, NC);
+  const int bpg = a->sl ? geo.NFG * geo.KS : geo.NFG;
   Ws w{reinterpret_cast<char*>(ws), ws_bytes};
-  EdgeGeo geo;
-  int bpg;
+  int* part = w.take<int>((size_t)G * bpg * NC);
+  float* ftp = geo.KS == 1 ? a->fiber_time : w.take<float>((size_t)geo.KS * geo.NS);
+  PF_REQUIRE(part && ftp, where, "workspace too small");
+  { pf::Timer tm_("schedule", st);
   if (a->sl) {
-    const pfsgnn_sliced_t& s = *a->sl;
-    const SlGeo sg{s.fib, s.base, s.len, s.cls, s.pco, s.EP, s.E, s.maxdeg};
-    geo = pfm::sl_geo(G, NF, NC, sg);
-    bpg = geo.NFG * geo.KS;   // every block holds every class
-    int* part = static_cast<int*>(w.take((size_t)G * bpg * NC * sizeof(int)));
-    float* ftp = geo.KS == 1 ? a->fiber_time
-                             : static_cast<float*>(w.take((size_t)geo.KS * geo.NS * sizeof(float)));
-    PF_REQUIRE(part && ftp, where, "workspace too small");
-    { pf::Timer tm_("schedule", st);
     LOSS_DISPATCH_F(F, hipLaunchKernelGGL(ksl_schedule<FF>, dim3(geo.nblocks), dim3(256), 0, st, geo,
                                           sg, a->pos_user, a->y, a->sc, a->sh, a->Wd1, a->bd1,
                                           a->Wd2, a->bd2, a->ci, a->scale, a->rounding, a->visits,
                                           ftp, part));
-    tm_.end(); }
-    hipLaunchKernelGGL(k_schedule_finish, dim3(G), dim3(256), 0, st, NF, NC, G * NC, bpg, geo.KS,
-                       geo.NS, part, ftp, a->ci, a->total_time, a->nfields, a->n_hard,
-                       a->fiber_time, a->completeness, a->utility, a->over, a->worst);
   } else {
-    geo = loss_geo(G, NF, NC);
-    bpg = geo.NFG;            // the class splits own disjoint classes
-    int* part = static_cast<int*>(w.take((size_t)G * bpg * NC * sizeof(int)));
-    float* ftp = geo.KS == 1 ? a->fiber_time
-                             : static_cast<float*>(w.take((size_t)geo.KS * geo.NS * sizeof(float)));
-    PF_REQUIRE(part && ftp, where, "workspace too small");
-    { pf::Timer tm_("schedule", st);
     LOSS_DISPATCH_F(F, hipLaunchKernelGGL(k_schedule<FF>, dim3(edge_grid(geo)), dim3(256), 0, st, geo,
                                           a->y, a->sc, a->sh, a->Wd1, a->bd1, a->Wd2, a->bd2, a->ci,
                                           a->scale, a->rounding, a->mode, a->perm, a->visits, ftp,
                                           part));
-    tm_.end(); }
-    hipLaunchKernelGGL(k_schedule_finish, dim3(G), dim3(256), 0, st, NF, NC, G * NC, bpg, geo.KS,
-                       geo.NS, part, ftp, a->ci, a->total_time, a->nfields, a->n_hard,
-                       a->fiber_time, a->completeness, a->utility, a->over, a->worst);
   }
+  tm_.end(); }
+  hipLaunchKernelGGL(k_schedule_finish, dim3(G), dim3(256), 0, st, NF, NC, G * NC, bpg, geo.KS,
+                     geo.NS, part, ftp, a->ci, a->total_time, a->nfields, a->n_hard, a->fiber_time,
+                     a->completeness, a->utility, a->over, a->worst);
   return pf::check_launch(where);
 }
 
@@ -356,8 +400,8 @@ extern "C" int pfsgnn_schedule(const pfsgnn_schedule_args* a, void* ws, size_t w
 namespace {
 // pfsgnn_schedule_budget (include/pfsgnn.h): largest-remainder apportionment per
 // fiber.  Two launches and the finish above:
-//   1. the quotient pass (k_budget_quot / ksl_budget_quot: k_schedule's and
-//      ksl_schedule's loaders and ownership) writes one 32-bit word per edge in
+//   1. the quotient pass (k_budget_quot / ksl_budget_quot: the dense and the
+//      sliced time pass above) writes one 32-bit word per edge in
 //      canonical or slot order -- the fp32 quotient q_e >= 0 (sign bit clear),
 //      or BQ_DONE | 0 for an inert edge or a padding slot -- and quot in the
 //      caller's order; with time_in there is no such launch, the selection
@@ -380,7 +424,7 @@ constexpr uint32_t BQ_DONE = 0x80000000u;
 
 __device__ __forceinline__ uint32_t budget_word(float time, float Ti, float* q_out) {
   const float v = time / Ti;                 // one IEEE division
-  const bool inert = !(v == v) || !(Ti > 0.f) || !(Ti < INFINITY);
+  const bool inert = !(v == v) || inert_T(Ti);
   const float q = inert ? 0.f : (v > 0.f ? fminf(v, 16777216.f) : 0.f);
   *q_out = q;
   return inert ? BQ_DONE : __float_as_uint(q);
@@ -397,26 +441,15 @@ __global__ __launch_bounds__(256) void k_budget_quot(
     float scale, int mode, const int32_t* __restrict__ perm, uint32_t* __restrict__ qws,
     float* __restrict__ quot) {
   EDGE_PROLOGUE
-  __shared__ __attribute__((aligned(16))) DecW<F> dw;
-  dw.load(Wd1, bd1, Wd2, bd2);
-  __syncthreads();
-  Y_PREFETCH_DECL(F)
-  CLASS_LOOP_BEGIN
-    float x[F];
-    Y_TAKE(F, x)
-    EdgeTime<F> L;
-    const float* dwp = dec_base(dw);
-    L.run(x, dwp, dwp + F * F, dwp + F * F + F, dwp + F * F + 2 * F, scale);
+  dense_time_pass<F>(geo, gg, f, fvalid, c0, c1, wave, y, sc, sh, Wd1, bd1, Wd2, bd2, scale,
+                     [&](float time, bool fvalid, long long cn, long long e, long long eu) {
     float q;
-    const uint32_t w = budget_word(L.time, ci[cn], &q);
+    const uint32_t w = budget_word(time, ci[cn], &q);
     if (fvalid) {
       qws[e] = w;                            // canonical: consecutive fibers, coalesced
-      if (quot) {
-        const long long u = mode == 2 ? e : (mode == 1 ? eu : (long long)perm[e]);
-        quot[u] = q;
-      }
+      if (quot) quot[caller_pos(mode, e, eu, perm)] = q;
     }
-  CLASS_LOOP_END
+  });
 }
 
 template <int F>
@@ -427,40 +460,15 @@ __global__ __launch_bounds__(256) void ksl_budget_quot(
     const float* __restrict__ ci, float scale, uint32_t* __restrict__ qws,
     float* __restrict__ quot) {
   SLL_PROLOGUE
-  (void)wave;
-  __shared__ __attribute__((aligned(16))) DecW<F> dw;
-  dw.load(Wd1, bd1, Wd2, bd2);
-  __syncthreads();
-  // (ksl_schedule's loader: the position opaque per iteration)
-  auto load = [&](int i) {
-    SlEdge<F> r;
-    r.in = k0 + 4 * i + q4 < k1;
-    long long p = p0 + 64ll * i;
-    asm volatile("" : "+v"(p));
-    r.cls = r.in ? (int)sl.cls[p] : 0xFF;
-    r.pos = r.in ? pos_user[p] : -1;
-    const float* yp = y + p;
-#pragma unroll
-    for (int k = 0; k < F; ++k) r.y[k] = r.in ? yp[(long long)k * EP] : 0.f;
-    return r;
-  };
-  SlEdge<F> cur = load(0);
-  for (int i = 0; i < nit; ++i) {
-    const SlEdge<F> nxt = load(i + 1);
-    SLL_STEP(cur)
-    float x[F];
-#pragma unroll
-    for (int k = 0; k < F; ++k) x[k] = sc ? fmaf(cur.y[k], sc[k], sh[k]) : cur.y[k];
-    EdgeTime<F> L;
-    const float* dwp = dec_base(dw);
-    L.run(x, dwp, dwp + F * F, dwp + F * F + F, dwp + F * F + 2 * F, scale);
+  sliced_time_pass<F>(geo, sl, gg, fib, q4, k0, k1, p0, pos_user, y, sc, sh, Wd1, bd1, Wd2, bd2,
+                      scale,
+                      [&](float time, bool ev, int, long long cn, const SlEdge<F>& ed, long long slot) {
     float q;
-    const uint32_t w = budget_word(L.time, ci[cn], &q);
+    const uint32_t w = budget_word(time, ci[cn], &q);
     // every slot of the split is written: padding and fiber-less lanes as final 0
-    if (cur.in) qws[p0 + 64ll * i] = ev ? w : BQ_DONE;
-    if (ev && quot) quot[cur.pos] = q;
-    cur = nxt;
-  }
+    if (ed.in) qws[slot] = ev ? w : BQ_DONE;
+    if (ev && quot) quot[ed.pos] = q;
+  });
 }
 
 // the words of the lane's fiber: dense, column `lane` of the LDS tile (step k =
@@ -588,7 +596,7 @@ __global__ __launch_bounds__(64) void k_budget_select(
   const long long e0 = (long long)gg * NC * NF + (fvalid ? f : 0);
   auto user = [&](int k) {
     const long long e = e0 + (long long)k * NF;
-    return mode == 2 ? e : (mode == 1 ? n * NC + k : (long long)perm[e]);
+    return caller_pos(mode, e, n * NC + k, perm);
   };
   double ft = 0.0;
   if (time_in) {
@@ -712,31 +720,14 @@ extern "C" int pfsgnn_schedule_budget(const pfsgnn_schedule_budget_args* a, void
                                       size_t ws_bytes, void* stream) {
   const char* where = "pfsgnn_schedule_budget";
   PF_REQUIRE(a, where, "null argument struct");
-  PF_REQUIRE(!a->sl == !a->pos_user, where,
-             "sl and pos_user go together (both set: a sliced general batch; both NULL: complete)");
-  PF_REQUIRE(!(a->sl && a->perm), where,
-             "sl with perm: a sliced batch maps its edges by pos_user, mode and perm are the "
-             "complete batch's");
-  PF_REQUIRE(a->sl || (a->mode >= 0 && a->mode <= 2), where, "mode must be 0 (perm), 1 or 2");
-  PF_REQUIRE(a->sl || a->mode != 0 || a->perm, where, "mode 0 needs perm");
   const int G = a->G, NF = a->NF, NC = a->NC, F = a->F;
-  PF_REQUIRE(F == 8 || F == 10 || F == 16, where, "unsupported Fdim (8, 10, 16)");
-  PF_REQUIRE(G > 0 && NF > 0 && NC > 0, where, "need G > 0, NF > 0, NC > 0");
+  if (int rc = check_batch(where, G, NF, NC, F, a->sl, a->pos_user, a->mode, a->perm)) return rc;
   if (a->sl) {
-    const pfsgnn_sliced_t* s = a->sl;
-    PF_REQUIRE(s->fib && s->base && s->len && s->cls && s->EP > 0 && s->E > 0 && s->EP >= s->E,
-               where, "bad sliced layout");
-    int m = 0;
-    if (pfsgnn_sliced_max_nc(F, &m) != 0 || m <= 0)
-      return pf::fail(where, "sliced layout: the current edge path has no sliced kernels");
-    PF_REQUIRE(NC <= m && NC <= MAXC, where,
-               "sliced layout: too many classes per graph (pfsgnn_sliced_max_nc)");
-    PF_REQUIRE(s->EP < (1ll << 31), where, "EP too large for int32 slot ids");
+    PF_REQUIRE(a->sl->EP < (1ll << 31), where, "EP too large for int32 slot ids");
   } else {
     PF_REQUIRE(NC <= BUDGET_MAX_NC, where,
                "too many classes per graph for the selection pass's LDS tile "
                "(pfsgnn_schedule_budget_max_nc)");
-    PF_REQUIRE((long long)G * NF * NC < (1ll << 31), where, "E too large for int32 edge ids");
   }
   PF_REQUIRE(a->visits && a->n_hard && a->fiber_time && a->completeness && a->utility && a->over &&
                  a->worst && a->phase,
@@ -748,12 +739,11 @@ extern "C" int pfsgnn_schedule_budget(const pfsgnn_schedule_budget_args* a, void
   Ws w{reinterpret_cast<char*>(ws), ws_bytes};
   const int NFG = (NF + 63) / 64;
   const long long slots = a->sl ? a->sl->EP : (long long)G * NF * NC;
-  uint32_t* qws = static_cast<uint32_t*>(w.take((size_t)slots * sizeof(uint32_t)));
-  int* part = static_cast<int*>(w.take((size_t)G * NFG * NC * sizeof(int)));
+  uint32_t* qws = w.take<uint32_t>((size_t)slots);
+  int* part = w.take<int>((size_t)G * NFG * NC);
   PF_REQUIRE(qws && part, where, "workspace too small (pfsgnn_schedule_budget_ws_bytes)");
   if (a->sl) {
-    const pfsgnn_sliced_t& s = *a->sl;
-    const SlGeo sg{s.fib, s.base, s.len, s.cls, s.pco, s.EP, s.E, s.maxdeg};
+    const SlGeo sg = sl_of(*a->sl);
     if (!a->time_in) {
       const EdgeGeo geo = pfm::sl_geo(G, NF, NC, sg);
       LOSS_DISPATCH_F(F, hipLaunchKernelGGL(ksl_budget_quot<FF>, dim3(geo.nblocks), dim3(256), 0, st,
@@ -847,7 +837,7 @@ __global__ __launch_bounds__(256) void k_plan_class(
   const int cn = blockIdx.x, t = threadIdx.x;
   const int gg = cn / NC, c = cn - gg * NC;
   const float T = ci[cn];
-  const bool inert = !(T > 0.f) || !(T < INFINITY);
+  const bool inert = inert_T(T);
   long long k0;
   int n;
   if (CSR) {
@@ -868,7 +858,7 @@ __global__ __launch_bounds__(256) void k_plan_class(
     const long long s = slot(k);
     long long u;
     if (CSR) u = user_of[s];
-    else u = mode == 2 ? s : (mode == 1 ? ((long long)gg * NF + k) * NC + c : (long long)perm[s]);
+    else u = caller_pos(mode, s, ((long long)gg * NF + k) * NC + c, perm);
     int v = visits_in[u];
     v = inert ? 0 : min(max(v, 0), PLAN_WMAX);
     w[s] = v;
@@ -969,7 +959,7 @@ __global__ __launch_bounds__(256) void k_plan_fiber(int NF, int NC, int NFB, lon
   for (int k = 0; k < NC; ++k) {
     const long long e = e0 + (long long)k * NF;   // canonical: consecutive fibers, coalesced
     const int v = w[e];
-    const long long u = mode == 2 ? e : (mode == 1 ? n * NC + k : (long long)perm[e]);
+    const long long u = caller_pos(mode, e, n * NC + k, perm);
     const double Td = (double)Tg[k];
     if (FILL) {
       plan_fill(o, i0 + c, v, (int)u, run, Td);
@@ -1056,8 +1046,6 @@ __global__ __launch_bounds__(256) void k_plan_finish(int NF, int NC,
                                                      int* __restrict__ over,
                                                      float* __restrict__ worst) {
   const int g = blockIdx.x, t = threadIdx.x;
-  __shared__ float smin[256], smax[256];
-  __shared__ int sover[256];
   float mn = INFINITY, mx = 0.f;
   int ov = 0;
   for (int c = t; c < NC; c += 256) mn = nan_min(mn, completeness[(long long)g * NC + c]);
@@ -1066,23 +1054,7 @@ __global__ __launch_bounds__(256) void k_plan_finish(int NF, int NC,
     mx = nan_max(mx, used[n]);
     ov += ovf[n];
   }
-  smin[t] = mn;
-  smax[t] = mx;
-  sover[t] = ov;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (t < s) {
-      smin[t] = nan_min(smin[t], smin[t + s]);
-      smax[t] = nan_max(smax[t], smax[t + s]);
-      sover[t] += sover[t + s];
-    }
-    __syncthreads();
-  }
-  if (t == 0) {
-    utility[g] = smin[0];
-    over[g] = sover[0];
-    worst[g] = smax[0];
-  }
+  graph_summary(mn, mx, ov, utility, over, worst);
 }
 
 int plan_key_bits(long long n) {  // keys are 0..n-1
@@ -1091,10 +1063,17 @@ int plan_key_bits(long long n) {  // keys are 0..n-1
   return b;
 }
 
+// the op's workspace: the words (general: the sort's input keys first, dead
+// once it has run), general only the sort's output keys and the plan order,
+// the fibers' counts (+ 1: the scan's total), their over flags, hipcub's scratch
 struct PlanWs {
-  size_t words, cnt, ovf, tmp, total;
+  int *w, *keyB, *pord;
+  long long* cnt;
+  int* ovf;
+  char* tmp;
+  size_t tmp_bytes;
 };
-PlanWs plan_ws(int G, int NF, int NC, long long E) {
+PlanWs plan_ws(Ws& ws, int G, int NF, int NC, long long E) {   // E = 0: a complete batch
   const long long NS = (long long)G * NF;
   const bool csr = E > 0;
   const long long edges = csr ? E : NS * NC;
@@ -1105,11 +1084,13 @@ PlanWs plan_ws(int G, int NF, int NC, long long E) {
     (void)hipcub::DeviceRadixSort::SortPairs(nullptr, tsort, (const int*)nullptr, (int*)nullptr,
                                              (const int*)nullptr, (int*)nullptr, (int)edges);
   PlanWs p;
-  p.words = align256((size_t)edges * sizeof(int));
-  p.cnt = align256((size_t)(NS + 1) * sizeof(long long));
-  p.ovf = align256((size_t)NS * sizeof(int));
-  p.tmp = align256(std::max(tscan, tsort)) + 256;
-  p.total = (csr ? 3 : 1) * p.words + p.cnt + p.ovf + p.tmp;
+  p.w = ws.take<int>((size_t)edges);
+  p.keyB = csr ? ws.take<int>((size_t)edges) : nullptr;
+  p.pord = csr ? ws.take<int>((size_t)edges) : nullptr;
+  p.cnt = ws.take<long long>((size_t)(NS + 1));
+  p.ovf = ws.take<int>((size_t)NS);
+  p.tmp_bytes = align256(std::max(tscan, tsort)) + 256;
+  p.tmp = ws.take<char>(p.tmp_bytes);
   return p;
 }
 
@@ -1121,7 +1102,9 @@ extern "C" size_t pfsgnn_schedule_plan_ws_bytes(int G, int NF, int NC, long long
   if (G <= 0 || NF <= 0 || NC <= 0 || E < 0 || E >= (1ll << 31) ||
       (long long)G * NF >= (1ll << 31) - 1 || (E == 0 && (long long)G * NF * NC >= (1ll << 31)))
     return 0;
-  return plan_ws(G, NF, NC, E).total;
+  Ws sizing{nullptr, 0};
+  plan_ws(sizing, G, NF, NC, E);
+  return sizing.used;
 }
 
 extern "C" int pfsgnn_schedule_plan(const pfsgnn_schedule_plan_args* a, void* ws, size_t ws_bytes,
@@ -1136,8 +1119,7 @@ extern "C" int pfsgnn_schedule_plan(const pfsgnn_schedule_plan_args* a, void* ws
   PF_REQUIRE(complete || any_csr, where,
              "neither batch form: mode = -1 needs the CSR arrays of pfsgnn_sparse_layout");
   if (complete) {
-    PF_REQUIRE(a->mode >= 0 && a->mode <= 2, where, "mode must be 0 (perm), 1 or 2");
-    PF_REQUIRE(a->mode != 0 || a->perm, where, "mode 0 needs perm");
+    if (int rc = check_mode(where, a->mode, a->perm)) return rc;
   } else {
     PF_REQUIRE(a->src_p && a->tgt_p && a->user_of && a->fib_ptr && a->cls_ord && a->cls_ptr, where,
                "the CSR form needs src_p, tgt_p, user_of, fib_ptr, cls_ord and cls_ptr");
@@ -1157,57 +1139,49 @@ extern "C" int pfsgnn_schedule_plan(const pfsgnn_schedule_plan_args* a, void* ws
   const long long E = complete ? NS * NC : a->E;
   PF_REQUIRE(E < (1ll << 31) && NS < (1ll << 31) - 1 && NT < (1ll << 31), where,
              "E too large for int32 edge ids (E, G*NF, G*NC < 2^31)");
-  const PlanWs p = plan_ws(G, NF, NC, complete ? 0 : E);
-  PF_REQUIRE(ws && ws_bytes >= p.total, where,
+  Ws wsp{static_cast<char*>(ws), ws_bytes};
+  const PlanWs p = plan_ws(wsp, G, NF, NC, complete ? 0 : E);
+  PF_REQUIRE(ws && wsp.used <= ws_bytes, where,
              "workspace too small (pfsgnn_schedule_plan_ws_bytes)");
   hipStream_t st = as_stream(stream);
-  char* wp = static_cast<char*>(ws);
-  int* keyA = reinterpret_cast<int*>(wp);
-  int* keyB = complete ? nullptr : reinterpret_cast<int*>(wp + p.words);
-  int* pord = complete ? nullptr : reinterpret_cast<int*>(wp + 2 * p.words);
-  wp += (complete ? 1 : 3) * p.words;
-  long long* cnt = reinterpret_cast<long long*>(wp);
-  int* ovf = reinterpret_cast<int*>(wp + p.cnt);
-  void* tmp = wp + p.cnt + p.ovf;
-  int* w = keyA;   // (general: the sort's input keys are dead once it has run)
   const bool fill = a->seg_cap > 0;
-  PlanOut o{a->visits, a->start, a->used, a->idle, cnt, ovf, a->seg_ptr, a->seg_cap,
+  PlanOut o{a->visits, a->start, a->used, a->idle, p.cnt, p.ovf, a->seg_ptr, a->seg_cap,
             a->seg_edge, a->seg_start};
   const unsigned egrid = (unsigned)std::max<long long>(1, std::min<long long>((E + 255) / 256, 8192));
   if (!complete) {
-    hipLaunchKernelGGL(k_plan_keys, dim3(egrid), dim3(256), 0, st, E, a->src_p, a->cls_ord, keyA);
-    size_t tb = p.tmp;
-    if (hipcub::DeviceRadixSort::SortPairs(tmp, tb, keyA, keyB, a->cls_ord, pord, (int)E, 0,
+    hipLaunchKernelGGL(k_plan_keys, dim3(egrid), dim3(256), 0, st, E, a->src_p, a->cls_ord, p.w);
+    size_t tb = p.tmp_bytes;
+    if (hipcub::DeviceRadixSort::SortPairs(p.tmp, tb, p.w, p.keyB, a->cls_ord, p.pord, (int)E, 0,
                                            plan_key_bits(NS), st) != hipSuccess)
       return pf::fail(where, "radix sort (plan order)");
     hipLaunchKernelGGL(k_plan_class<true>, dim3((unsigned)NT), dim3(256), 0, st, NF, NC, (int)NT,
                        -1, nullptr, a->cls_ord, a->cls_ptr, a->user_of, a->ci, a->nfields, a->cap,
-                       a->visits_in, w, a->n_hard, a->completeness, a->cut);
+                       a->visits_in, p.w, a->n_hard, a->completeness, a->cut);
     hipLaunchKernelGGL(k_plan_fiber_csr<false>, dim3((unsigned)((NS + 3) / 4)), dim3(256), 0, st,
-                       NS, a->fib_ptr, pord, a->tgt_p, a->user_of, w, a->ci, a->total_time, o);
+                       NS, a->fib_ptr, p.pord, a->tgt_p, a->user_of, p.w, a->ci, a->total_time, o);
   } else {
     const int NFB = (NF + 255) / 256;
     hipLaunchKernelGGL(k_plan_class<false>, dim3((unsigned)NT), dim3(256), 0, st, NF, NC, (int)NT,
                        a->mode, a->perm, nullptr, nullptr, nullptr, a->ci, a->nfields, a->cap,
-                       a->visits_in, w, a->n_hard, a->completeness, a->cut);
+                       a->visits_in, p.w, a->n_hard, a->completeness, a->cut);
     hipLaunchKernelGGL(k_plan_fiber<false>, dim3((unsigned)(G * NFB)), dim3(256), 0, st, NF, NC,
-                       NFB, NS, a->mode, a->perm, w, a->ci, a->total_time, o);
+                       NFB, NS, a->mode, a->perm, p.w, a->ci, a->total_time, o);
   }
   hipLaunchKernelGGL(k_plan_finish, dim3(G), dim3(256), 0, st, NF, NC, a->completeness, a->used,
-                     ovf, a->utility, a->over, a->worst);
+                     p.ovf, a->utility, a->over, a->worst);
   {
-    size_t tb = p.tmp;
-    if (hipcub::DeviceScan::ExclusiveSum(tmp, tb, cnt, a->seg_ptr, (int)(NS + 1), st) != hipSuccess)
+    size_t tb = p.tmp_bytes;
+    if (hipcub::DeviceScan::ExclusiveSum(p.tmp, tb, p.cnt, a->seg_ptr, (int)(NS + 1), st) != hipSuccess)
       return pf::fail(where, "scan (segment offsets)");
   }
   if (fill) {
     if (!complete) {
       hipLaunchKernelGGL(k_plan_fiber_csr<true>, dim3((unsigned)((NS + 3) / 4)), dim3(256), 0, st,
-                         NS, a->fib_ptr, pord, a->tgt_p, a->user_of, w, a->ci, a->total_time, o);
+                         NS, a->fib_ptr, p.pord, a->tgt_p, a->user_of, p.w, a->ci, a->total_time, o);
     } else {
       const int NFB = (NF + 255) / 256;
       hipLaunchKernelGGL(k_plan_fiber<true>, dim3((unsigned)(G * NFB)), dim3(256), 0, st, NF, NC,
-                         NFB, NS, a->mode, a->perm, w, a->ci, a->total_time, o);
+                         NFB, NS, a->mode, a->perm, p.w, a->ci, a->total_time, o);
     }
   }
   return pf::check_launch(where);

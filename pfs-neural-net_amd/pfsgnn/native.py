@@ -1631,6 +1631,53 @@ class HipBackend:
         _call("pfsgnn_loss_fwd", ctypes.byref(a), ws, wsb, _stream())
         return n_prime, fiber_time, tmean, tvar, tt
 
+    # ---- the schedule ops (pfsgnn_schedule, _budget, _plan): what their wrappers share
+    def _sched_out(self, a, d, fields, out, E=None):
+        """Allocate (``out`` None), check and bind an op's outputs.  ``fields``
+        names them in the order of the returned tuple; an output's length and
+        dtype follow from its name."""
+        E = d.E if E is None else E
+        f32, i32, i64 = torch.float32, torch.int32, torch.int64
+        spec = dict(visits=(E, i32), quot=(E, f32), start=(E, f32), n_hard=(d.NT, i32),
+                    completeness=(d.NT, f32), cut=(d.NT, i64), fiber_time=(d.NS, f32),
+                    used=(d.NS, f32), idle=(d.NS, f32), phase=(d.NS, i32), seg_ptr=(d.NS + 1, i64),
+                    utility=(d.G, f32), over=(d.G, i32), worst=(d.G, f32))
+        if out is None:
+            out = tuple(torch.empty(spec[k][0], dtype=spec[k][1], device=self.device)
+                        for k in fields)
+        assert len(out) == len(fields)
+        for k, t in zip(fields, out):
+            n, dt = spec[k]
+            assert t.dtype == dt and t.is_cuda and t.is_contiguous(), (k, t.dtype, t.device)
+            assert t.numel() == n, (k, t.numel(), n)
+            setattr(a, k, t.data_ptr())
+        return out
+
+    @staticmethod
+    def _sched_batch(a, sl, mode, perm, E):
+        """The batch form: sliced (``sl`` + its pos_user), or complete (``mode``, ``perm``)."""
+        if sl is not None:
+            a.sl, a.pos_user = sl.ref, sl.pos_user.data_ptr()
+            return
+        a.mode = int(mode)
+        if perm is not None:
+            assert perm.dtype == torch.int32 and perm.is_cuda and perm.numel() == E
+            a.perm = perm.data_ptr()
+
+    def _sched_in(self, a, d, y, sc, sh, Wd1, bd1, Wd2, bd2, ci, scale, total_time, nfields):
+        """The lazy edge state, the decoder, the class table and the scalars
+        (the edge state and the decoder may be None: ``time_in``)."""
+        self._chk(y, sc, sh, Wd1, bd1, Wd2, bd2)
+        assert y is None or tuple(y.shape) == (d.F, d.EP), (tuple(y.shape), d.F, d.EP)
+        ci = ci.contiguous()
+        assert ci.numel() >= 2 * d.NT
+        for k, v in dict(y=y, sc=sc, sh=sh, Wd1=Wd1, bd1=bd1, Wd2=Wd2, bd2=bd2, ci=ci).items():
+            setattr(a, k, _ptr(v))
+        a.scale, a.total_time, a.nfields = float(scale), float(total_time), float(nfields)
+        return ci   # (kept alive by the caller until the launch is queued)
+
+    SCHEDULE_FIELDS = ("visits", "n_hard", "fiber_time", "completeness", "utility", "over", "worst")
+
     def schedule(self, d, y, sc, sh, Wd1, bd1, Wd2, bd2, ci, scale, total_time, nfields,
                  rounding=0, mode=1, perm=None, out=None):
         """The hard visit counts of the lazy edge state (pfsgnn_schedule) ->
@@ -1640,35 +1687,11 @@ class HipBackend:
         order (0: perm, 1: fiber-major, 2: canonical); a sliced general batch
         (``d.sp.sl``): y [F, EP] in slot order.  ``out``: the seven tensors to
         write into (a loop's preallocated buffers)."""
-        sl = self._loss_layout(d)
-        if out is None:
-            i32 = dict(dtype=torch.int32, device=self.device)
-            out = (torch.empty(d.E, **i32), torch.empty(d.NT, **i32), self.empty(d.NS),
-                   self.empty(d.NT), self.empty(d.G), torch.empty(d.G, **i32), self.empty(d.G))
-        visits, n_hard, fiber_time, comp, utility, over, worst = out
-        assert visits.dtype == n_hard.dtype == over.dtype == torch.int32
-        self._chk(y, sc, sh, Wd1, bd1, Wd2, bd2, fiber_time, comp, utility, worst)
-        assert all(t.is_cuda and t.is_contiguous() for t in (visits, n_hard, over))
-        assert visits.numel() == d.E and n_hard.numel() == comp.numel() == d.NT
-        assert fiber_time.numel() == d.NS and min(utility.numel(), over.numel(), worst.numel()) == d.G
-        assert tuple(y.shape) == (d.F, d.EP), (tuple(y.shape), d.F, d.EP)
-        ci = ci.contiguous()
-        assert ci.numel() >= 2 * d.NT
+        assert y is not None
         a = ScheduleArgs(G=d.G, NF=d.NF, NC=d.NC, F=d.F, rounding=int(rounding))
-        if sl is not None:
-            a.sl, a.pos_user = sl.ref, sl.pos_user.data_ptr()
-        else:
-            a.mode = int(mode)
-            if perm is not None:
-                assert perm.dtype == torch.int32 and perm.is_cuda and perm.numel() == d.E
-                a.perm = perm.data_ptr()
-        a.y, a.sc, a.sh = y.data_ptr(), _ptr(sc), _ptr(sh)
-        a.Wd1, a.bd1, a.Wd2, a.bd2 = Wd1.data_ptr(), bd1.data_ptr(), Wd2.data_ptr(), bd2.data_ptr()
-        a.ci = ci.data_ptr()
-        a.scale, a.total_time, a.nfields = float(scale), float(total_time), float(nfields)
-        for k, v in zip(("visits", "n_hard", "fiber_time", "completeness", "utility", "over",
-                         "worst"), out):
-            setattr(a, k, v.data_ptr())
+        out = self._sched_out(a, d, self.SCHEDULE_FIELDS, out)
+        self._sched_batch(a, self._loss_layout(d), mode, perm, d.E)
+        ci = self._sched_in(a, d, y, sc, sh, Wd1, bd1, Wd2, bd2, ci, scale, total_time, nfields)
         ws, wsb = self._wsargs(d)
         _call("pfsgnn_schedule", ctypes.byref(a), ws, wsb, _stream())
         return out
@@ -1686,37 +1709,15 @@ class HipBackend:
         (bit 0: down phase, 1: bumped, 2: refused a candidate).  ``out``: the nine
         tensors to write into."""
         sl = self._loss_layout(d)
-        i32 = dict(dtype=torch.int32, device=self.device)
-        if out is None:
-            out = (torch.empty(d.E, **i32), torch.empty(d.NT, **i32), self.empty(d.NS),
-                   self.empty(d.NT), self.empty(d.G), torch.empty(d.G, **i32), self.empty(d.G),
-                   self.empty(d.E), torch.empty(d.NS, **i32))
-        visits, n_hard, fiber_time, comp, utility, over, worst, quot, phase = out
-        assert visits.dtype == n_hard.dtype == over.dtype == phase.dtype == torch.int32
-        self._chk(y, sc, sh, Wd1, bd1, Wd2, bd2, time_in, fiber_time, comp, utility, worst, quot)
-        assert all(t.is_cuda and t.is_contiguous() for t in (visits, n_hard, over, phase))
-        assert visits.numel() == quot.numel() == d.E and n_hard.numel() == comp.numel() == d.NT
-        assert fiber_time.numel() == phase.numel() == d.NS
-        assert min(utility.numel(), over.numel(), worst.numel()) == d.G
-        assert time_in is not None or tuple(y.shape) == (d.F, d.EP), (d.F, d.EP)
-        assert time_in is None or time_in.numel() == d.E
-        ci = ci.contiguous()
-        assert ci.numel() >= 2 * d.NT
+        assert time_in is not None or y is not None
         a = ScheduleBudgetArgs(G=d.G, NF=d.NF, NC=d.NC, F=d.F)
-        if sl is not None:
-            a.sl, a.pos_user = sl.ref, sl.pos_user.data_ptr()
-        else:
-            a.mode = int(mode)
-            if perm is not None:
-                assert perm.dtype == torch.int32 and perm.is_cuda and perm.numel() == d.E
-                a.perm = perm.data_ptr()
-        for k, v in dict(y=y, sc=sc, sh=sh, Wd1=Wd1, bd1=bd1, Wd2=Wd2, bd2=bd2, ci=ci,
-                         time_in=time_in).items():
-            setattr(a, k, _ptr(v))
-        a.scale, a.total_time, a.nfields = float(scale), float(total_time), float(nfields)
-        for k, v in zip(("visits", "n_hard", "fiber_time", "completeness", "utility", "over",
-                         "worst", "quot", "phase"), out):
-            setattr(a, k, v.data_ptr())
+        out = self._sched_out(a, d, self.SCHEDULE_FIELDS + ("quot", "phase"), out)
+        self._sched_batch(a, sl, mode, perm, d.E)
+        ci = self._sched_in(a, d, y, sc, sh, Wd1, bd1, Wd2, bd2, ci, scale, total_time, nfields)
+        if time_in is not None:
+            self._chk(time_in)
+            assert time_in.numel() == d.E
+            a.time_in = time_in.data_ptr()
         need = lib().pfsgnn_schedule_budget_ws_bytes(d.G, d.NF, d.NC, 0 if sl is None else sl.EP)
         ws, wsb = self._wsargs(d, need)
         _call("pfsgnn_schedule_budget", ctypes.byref(a), ws, wsb, _stream())
@@ -1740,46 +1741,27 @@ class HipBackend:
         ``out``: the eleven tensors to write into."""
         sp = d.sp if sp is None else sp
         E = d.E if sp is None else sp.E
-        i32 = dict(dtype=torch.int32, device=self.device)
-        i64 = dict(dtype=torch.int64, device=self.device)
-        if out is None:
-            out = (torch.empty(E, **i32), self.empty(E), self.empty(d.NS), self.empty(d.NS),
-                   torch.empty(d.NT, **i32), self.empty(d.NT), self.empty(d.G),
-                   torch.empty(d.G, **i32), self.empty(d.G), torch.empty(d.NT, **i64),
-                   torch.empty(d.NS + 1, **i64))
-        visits, start, used, idle, n_hard, comp, utility, over, worst, cut, seg_ptr = out
-        assert visits.dtype == n_hard.dtype == over.dtype == torch.int32
-        assert cut.dtype == seg_ptr.dtype == torch.int64
-        self._chk(start, used, idle, comp, utility, worst, seg_start)
-        assert all(t.is_cuda and t.is_contiguous() for t in (visits, n_hard, over, cut, seg_ptr))
-        assert visits.numel() == start.numel() == E and used.numel() == idle.numel() == d.NS
-        assert n_hard.numel() == comp.numel() == cut.numel() == d.NT
-        assert min(utility.numel(), over.numel(), worst.numel()) == d.G
-        assert seg_ptr.numel() == d.NS + 1
+        a = PlanArgs(G=d.G, NF=d.NF, NC=d.NC, cap=int(bool(cap)))
+        out = self._sched_out(a, d, self.PLAN_FIELDS, out, E)
         assert (visits_in.dtype == torch.int32 and visits_in.is_cuda and visits_in.is_contiguous()
                 and visits_in.numel() == E)
         ci = ci.contiguous()
         assert ci.numel() >= 2 * d.NT
-        a = PlanArgs(G=d.G, NF=d.NF, NC=d.NC, cap=int(bool(cap)))
         if sp is not None:
             a.mode, a.E = -1, E
             for k in ("src_p", "tgt_p", "user_of", "fib_ptr", "cls_ord", "cls_ptr"):
                 setattr(a, k, getattr(sp, k).data_ptr())
         else:
-            a.mode = int(mode)
-            if perm is not None:
-                assert perm.dtype == torch.int32 and perm.is_cuda and perm.numel() == E
-                a.perm = perm.data_ptr()
+            self._sched_batch(a, None, mode, perm, E)
         a.ci, a.visits_in = ci.data_ptr(), visits_in.data_ptr()
         a.total_time, a.nfields = float(total_time), float(nfields)
         if seg_edge is not None or seg_start is not None:
+            self._chk(seg_start)
             assert seg_edge.dtype == torch.int32 and seg_edge.is_cuda and seg_edge.is_contiguous()
             assert seg_edge.numel() == seg_start.numel()
             a.seg_cap = seg_edge.numel()
             if a.seg_cap:
                 a.seg_edge, a.seg_start = seg_edge.data_ptr(), seg_start.data_ptr()
-        for k, v in zip(self.PLAN_FIELDS, out):
-            setattr(a, k, v.data_ptr())
         need = lib().pfsgnn_schedule_plan_ws_bytes(d.G, d.NF, d.NC, 0 if sp is None else E)
         ws, wsb = self._wsargs(None, need)
         _call("pfsgnn_schedule_plan", ctypes.byref(a), ws, wsb, _stream())

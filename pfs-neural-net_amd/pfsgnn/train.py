@@ -328,22 +328,16 @@ def _hard_schedule(graph, class_info, rounding, gnn, out, time=None):
         time = torch.as_tensor(time, dtype=be.dtype, device=ci.device).reshape(-1).contiguous()
         if time.numel() != d.E:
             raise ValueError(f"time has {time.numel()} entries for {d.E} edges")
-    if budget and hasattr(be, "schedule_budget"):
+    op, Result, extra = (("schedule_budget", BudgetSchedule, dict(time_in=time)) if budget else
+                         ("schedule", HardSchedule, dict(rounding=_ROUNDINGS[rounding])))
+    if hasattr(be, op):
         P = model._flat_params()
         y, sc, sh = (None, None, None) if time is not None else xe3
-        res = be.schedule_budget(d, y, sc, sh, P["decoder_e.0.weight"], P["decoder_e.0.bias"],
-                                 P["decoder_e.2.weight"], P["decoder_e.2.bias"], ci, scale,
-                                 float(config.TOTAL_TIME), float(config.NFIELDS), mode=lay.mode,
-                                 perm=lay.perm, time_in=time, out=out)
-        return BudgetSchedule(*res)
-    if not budget and hasattr(be, "schedule"):
-        P = model._flat_params()
-        y, sc, sh = xe3
-        res = be.schedule(d, y, sc, sh, P["decoder_e.0.weight"], P["decoder_e.0.bias"],
-                          P["decoder_e.2.weight"], P["decoder_e.2.bias"], ci, scale,
-                          float(config.TOTAL_TIME), float(config.NFIELDS),
-                          rounding=_ROUNDINGS[rounding], mode=lay.mode, perm=lay.perm, out=out)
-        return HardSchedule(*res)
+        res = getattr(be, op)(d, y, sc, sh, P["decoder_e.0.weight"], P["decoder_e.0.bias"],
+                              P["decoder_e.2.weight"], P["decoder_e.2.bias"], ci, scale,
+                              float(config.TOTAL_TIME), float(config.NFIELDS), mode=lay.mode,
+                              perm=lay.perm, out=out, **extra)
+        return Result(*res)
     # a backend without the op (a CPU emulation of the op set): torch restatement
     with torch.no_grad():
         src, tgt = graph.edge_index[0], graph.edge_index[1]
